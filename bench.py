@@ -1,7 +1,15 @@
 """Benchmark: batched pkg/sat resolution on MI355X, host memory to host memory.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5]
-                    [--scaling weak|strong]
+                    [--scaling weak|strong] [--dump-outputs DIR] [--full]
+
+A plain run sets up the batch, warms up, times the K steps behind `value` and
+prints the line; every secondary figure and check below (`kernel_only`,
+`roofline`, `host_lowering_res_per_s`, `end_to_end`, `end_to_end_device`,
+`solve_batch_api`, `latency`, `cpu_baseline`, `deterministic`, the parity
+check against the oracle, `inproc`) takes runs of its own and is measured only
+with --full.  --dump-outputs DIR writes what the last timed step returned
+(dump_outputs).
 
 The reference's Solve is a host-memory-to-host-memory call
 (pkg/sat/solve.go:53-119).  Its benchmark times NewSolver(WithInput(...)) and
@@ -267,19 +275,22 @@ def cpu_end_to_end(wa, lw32, n, threads, seconds):
     return reps * n / (time.perf_counter() - t0)
 
 
-def lowered_config(config, n, seed, form="packed"):
+def lowered_config(config, n, seed, form="packed", full=True):
     """The batch lowered twice: in the packed 16-bit form into page-locked
     memory (dp_lower_into DP_LOWER_NARROW | DP_LOWER_PACKED | DP_LOWER_PINNED,
     as a serving loop keeps its lowering storage; what the GPU path is given)
     and as int32 records (what the CPU baseline is given).  Also the steady-state lowering rate
-    (dp_lower_into reusing its storage, the wire format -> records)."""
+    (dp_lower_into reusing its storage, the wire format -> records).  full=False
+    (a plain run): the packed records alone, nothing timed (-> lw, None, None, wa)."""
     from deppy_amd import _lib
     w = _lib.generate(config, n, seed)
     wa = _lib.WireArrays(**{k: w[k] for k in (
         "prob_var_off", "var_id", "var_con_off", "con_kind", "con_n", "con_arg_off", "con_arg",
         "str_off")}, str_bytes=w["str_bytes"].tobytes())
-    lw32 = _lib.Lowered(wa)
     lw = _lib.Lowered(wa, narrow=form != "i32", pinned=True, packed=form in ("packed", "p16d"), p8=form != "p16d")
+    if not full:
+        return lw, None, None, wa
+    lw32 = _lib.Lowered(wa)
     reps, t0 = 0, time.perf_counter()
     while reps < 3 or time.perf_counter() - t0 < 1.0:
         lw.relower(wa)
@@ -361,8 +372,50 @@ def same_results(a, b) -> bool:
     return True
 
 
+DUMP_KEYS = ("status", "flags", "installed", "inst_off", "core", "core_off", "core_len", "steps")
+DUMP_MAX_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(dirname, out, n, suffix="", max_bytes=DUMP_MAX_BYTES):
+    """Write a result dict (what dp_submit/dp_job_wait hands its caller) as
+    DIR/<name><suffix>.npy, float64 (every integer here is exact in it): the
+    per-problem arrays cut to the n problems, and `core` as the identities the
+    call defines (core_len[p] entries from core_off[p], problem after problem;
+    the words behind them are storage the call leaves as it found it).  At
+    most max_bytes in all: an array over its equal share is written as a
+    fixed sample (its elements at sorted indices drawn by a generator seeded
+    with 0, the same for every run with the same arguments)."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {}
+    for k in DUMP_KEYS:
+        a = np.asarray(out[k])
+        if k in ("status", "flags", "core_len", "steps"):
+            a = a[:n]
+        elif k == "core":
+            off, ln = np.asarray(out["core_off"])[:n], np.asarray(out["core_len"])[:n].astype(np.int64)
+            start = np.repeat(off - (np.cumsum(ln) - ln), ln)
+            a = a[start + np.arange(int(ln.sum()))]
+        arrays[k] = a
+    share = max_bytes // 8 // len(arrays)
+    written = {}
+    for k, a in arrays.items():
+        if len(a) > share:
+            a = a[np.sort(np.random.default_rng(0).choice(len(a), share, replace=False))]
+        a = a.astype(np.float64)
+        np.save(os.path.join(dirname, k + suffix + ".npy"), a)
+        written[k] = a
+    return written
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside value (kernel-only rate and roofline, "
+                         "lowering rates, end-to-end legs, latency, CPU baseline, determinism and parity "
+                         "against the oracle, the one-process multi-GPU leg); a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the results of the last timed step as DIR/<name>.npy "
+                         "(float64; rank r > 0 of a torchrun run writes <name>.rank<r>.npy)")
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--inproc", action="store_true",
                     help="one process drives the N GPUs (dp_create(n_devices=N), the cgo shim's topology) "
@@ -400,6 +453,11 @@ def main():
                     help="SQ instruction counts per wave of this build (scripts/pmc_sq_r02.sh + sq_summary.py), "
                          "for roofline.issue")
     args = ap.parse_args()
+    full = args.full
+    if args.kernel_only and not full:
+        ap.error("--kernel-only measures the kernel-only leg, one of --full's: give --full as well")
+    if args.kernel_only and args.dump_outputs:
+        ap.error("--dump-outputs writes the timed host-to-host path's results; --kernel-only has no timed steps")
     maybe_relaunch(args)
 
     from deppy_amd import _lib, shard  # noqa: E402  (after the relaunch decision)
@@ -417,7 +475,7 @@ def main():
         total = args.problems or wl[1]
         lo, hi = shard.strong_range(total, rank, world)
         n, first = hi - lo, args.seed + lo
-    lw, lw32, t_lower, wa = lowered_config(args.config, n, first, args.record_form)
+    lw, lw32, t_lower, wa = lowered_config(args.config, n, first, args.record_form, full)
     ctx = _lib.Context(0 if nd > 1 else local, nd, flags=args.flags)
     global LANES
     LANES = ctx.lanes()
@@ -448,7 +506,8 @@ def main():
         per_device = None
     else:
         run_steps(max(args.warmup, 1))
-        first_res = ctx.submit(lw.rec_off, lw.rec).wait()  # cold-free single call, for the check
+        if full:
+            first_res = ctx.submit(lw.rec_off, lw.rec).wait()  # cold-free single call, for the check
         g.barrier()
         ctx.stats(reset=True)
         t0 = time.perf_counter()
@@ -458,10 +517,19 @@ def main():
         per_device = [int(ctx.device_stats(d)["chunks"]) for d in range(nd)]
         st = ctx.stats(reset=True)
         elapsed = g.max(t1 - t0)
-        res = ctx.submit(lw.rec_off, lw.rec).wait()
-        deterministic = same_results(res, first_res) and all(
-            same_results(res, {**o, "status": o["status"][:n], "flags": o["flags"][:n],
-                               "core_len": o["core_len"][:n], "steps": o["steps"][:n]}) for o in outs)
+        # what the last timed step returned to its caller
+        last = outs[(args.steps - 1) % depth]
+        last = {**last, "status": last["status"][:n], "flags": last["flags"][:n],
+                "core_len": last["core_len"][:n], "steps": last["steps"][:n]}
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, last, n, ".rank%d" % rank if rank else "")
+        if full:
+            res = ctx.submit(lw.rec_off, lw.rec).wait()
+            deterministic = same_results(res, first_res) and all(
+                same_results(res, {**o, "status": o["status"][:n], "flags": o["flags"][:n],
+                                   "core_len": o["core_len"][:n], "steps": o["steps"][:n]}) for o in outs)
+        else:
+            res, deterministic = last, None
 
     value = world * n * args.steps / elapsed if args.scaling == "weak" else \
         (args.problems or wl[1]) * args.steps / elapsed
@@ -507,12 +575,15 @@ def main():
                         "footprints, leaves the counter out to stay spill-free)"},
         "records_pinned": bool(lw.pinned),
         "classes": class_mix(res) if res is not None else None,
-        "deterministic": bool(deterministic),
         "build": _lib.build_info(),
-        "host_lowering_res_per_s": round(n / t_lower, 1),
-        "host_lowering_note": "dp_lower_into (packed 16-bit records, storage reused) on the host pool; not in value",
+        "full": full,
     }
-    if not args.kernel_only and args.e2e_steps > 0:
+    if full:
+        line["deterministic"] = bool(deterministic)
+        line["host_lowering_res_per_s"] = round(n / t_lower, 1)
+        line["host_lowering_note"] = ("dp_lower_into (packed 16-bit records, storage reused) on the host pool; "
+                                      "not in value")
+    if full and not args.kernel_only and args.e2e_steps > 0:
         line["end_to_end"] = {
             "res_per_s": round(end_to_end(ctx, wa, n, args.e2e_steps), 1),
             "steps": args.e2e_steps,
@@ -538,11 +609,11 @@ def main():
         line["solve_batch_api"]["device_lowering_note"] = (
             "the same from the compact wire (sat.solve_wire on a Wire32Arrays: dp_lower_device + dp_solve)")
 
-    if args.kernel_steps > 0:
+    if full and args.kernel_steps > 0:
         # the solve kernel alone, records resident in HBM (dp_upload): serial
         # launches give the per-launch device time the roofline uses (HIP
         # events on the launch's stream; rocprofv3 --kernel-trace of
-        # `bench.py --kernel-only` reports the same kernels), then one batch
+        # `bench.py --full --kernel-only` reports the same kernels), then one batch
         # per pipeline lane in flight gives the rate the kernel sustains
         kdepth = args.kernel_depth or LANES
         slots = [ctx.upload(lw.rec_off, lw.rec) for _ in range(1 if args.kernel_only else kdepth)]
@@ -606,7 +677,7 @@ def main():
             "achieved": round(sus, 3), "frac": round(sus / HBM_PEAK_GBS, 6), "ms_per_batch": round(tk / ksteps * 1e3, 4),
             "note": "algorithmic bytes / kernel_only.ms_per_step (%d batches in flight)" % kdepth}
 
-    if rank == 0 and not args.no_cpu:
+    if full and rank == 0 and not args.no_cpu:
         from oracle import oracle  # CPU baseline + checker only
         share = cpu_share()
         threads = share["cores"]
@@ -683,7 +754,7 @@ def main():
                                               % threads)
         line["verified_bit_exact_vs_oracle"] = bool(ok)
         line["verified_note"] = "GPU on the packed 16-bit records vs oracle on the int32 records, every field incl. cores"
-    if world > 1 and not args.no_inproc_leg and args.scaling == "weak" and not args.kernel_only:
+    if full and world > 1 and not args.no_inproc_leg and args.scaling == "weak" and not args.kernel_only:
         # the shipped one-process topology on the same node, after the timed
         # region: rank 0 drives all N GPUs while the other ranks wait
         g.barrier()

@@ -1,7 +1,7 @@
 """Summarise scripts/pmc_fetch_split.sh: per config, the solve kernel's
 L2-to-fabric reads by request size, their destinations, its writes, the
 SQC's instruction / scalar-data requests and the L2 hit rate, per run of the
-batch (bench.py --kernel-only runs the batch K + 1 times).
+batch (bench.py --full --kernel-only runs the batch K + 1 times).
 
 Bytes: 32 B, 64 B and 128 B read requests at their sizes (gfx950 has a
 counter per size; FETCH_SIZE tallies every request that is not 32 B at 64 B,

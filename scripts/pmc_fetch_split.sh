@@ -1,6 +1,6 @@
 #!/bin/bash
 # Where the solve kernel's L2-to-fabric traffic comes from, per config
-# (bench.py --kernel-only: records resident in HBM, serial launches).  One
+# (bench.py --full --kernel-only: records resident in HBM, serial launches).  One
 # rocprofv3 --pmc pass per counter group, each under its own kill timeout:
 #   size  TCC_EA0_RDREQ by request size (32 / 64 / 128 B) and in total
 #   dest  reads served by DRAM, 32 B reads by destination, uncached reads
@@ -18,7 +18,7 @@ pass() {  # pass <cfg> <name> <counters...>
   local cfg=$1 name=$2; shift 2
   local ks=6; [ $cfg = 4 ] && ks=2
   timeout -s KILL 90 rocprofv3 --pmc "$@" --output-format csv -d $OUT/c${cfg}_$name -o run -- \
-    python3 bench.py --config $cfg --kernel-only --kernel-steps $ks --no-cpu > $OUT/c${cfg}_$name.json 2> $OUT/c${cfg}_$name.err \
+    python3 bench.py --full --config $cfg --kernel-only --kernel-steps $ks --no-cpu > $OUT/c${cfg}_$name.json 2> $OUT/c${cfg}_$name.err \
     || { echo "pass $name of config $cfg failed"; return 1; }
 }
 for cfg in ${1:-3 6 2}; do

@@ -18,7 +18,7 @@ if [ "$MODE" = tests ]; then
   cat $OUT/smoke.log
 fi
 for c in $CONFIGS; do
-  timeout -k 10 400 python -u bench.py --gpus 1 --steps 20 --warmup 5 --config $c > $OUT/bench_c$c.json 2> $OUT/bench_c$c.err || exit 1
+  timeout -k 10 400 python -u bench.py --full --gpus 1 --steps 20 --warmup 5 --config $c > $OUT/bench_c$c.json 2> $OUT/bench_c$c.err || exit 1
   python3 -c "import json; d=json.loads(open('$OUT/bench_c$c.json').read().strip().splitlines()[-1]); print('config $c', d['value'], 'kernel_only', d['kernel_only']['res_per_s'], 'frac', d['roofline']['frac'], 'lat', d['latency']['gpu_ms_median'], d['latency']['cpu_1thread_ms_median'], 'e2e', d.get('end_to_end', {}).get('res_per_s'), 'api', d.get('solve_batch_api', {}).get('res_per_s'), 'place', d['config'].get('placements'), 'h2d/step', d['pcie']['h2d_bytes_per_step'], 'exact', d['verified_bit_exact_vs_oracle'])"
 done
 if [[ " $CONFIGS " == *" 4 "* ]]; then
@@ -28,6 +28,6 @@ fi
 for c in $CONFIGS; do
   ks=10; [ $c = 4 ] && ks=4
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ktrace_c$c -o run -- \
-    python3 bench.py --config $c --kernel-only --kernel-steps $ks --no-cpu > $OUT/ktrace_c$c.json 2> $OUT/ktrace_c$c.err || exit 1
+    python3 bench.py --full --config $c --kernel-only --kernel-steps $ks --no-cpu > $OUT/ktrace_c$c.json 2> $OUT/ktrace_c$c.err || exit 1
 done
 echo "r06 gpu call done"
