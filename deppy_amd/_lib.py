@@ -96,6 +96,7 @@ EXPORTS = [
     "dp_gen_free", "dp_upload_traced", "dp_download_trace", "dp_solve_traced", "dp_lowered_errors",
     "dp_device_bytes", "dp_lower_into", "dp_lowered_new", "dp_lowered_exact_count", "dp_lowered_pinned", "dp_rec_widen", "dp_submit", "dp_job_wait", "dp_get_stats", "dp_stage_roundtrip",
     "dp_stitch_selftest", "dp_partition", "dp_build_info", "dp_get_device_stats", "dp_plan_placements",
+    "dp_plan_footprints", "dp_lds_occupancy",
     "dp_plan_order", "dp_dlower_new", "dp_dlower_free", "dp_lower_device", "dp_dlower_host_count",
     "dp_host_alloc", "dp_host_free",
 ]
@@ -282,6 +283,8 @@ def lib():
     L.dp_host_alloc.restype = vp
     L.dp_host_free.argtypes = [vp]
     L.dp_plan_placements.argtypes = [ctypes.POINTER(Batch), ctypes.c_int32, c_i8p]
+    L.dp_plan_footprints.argtypes = [ctypes.POINTER(Batch), ctypes.c_int32, c_i32p, c_i32p]
+    L.dp_lds_occupancy.argtypes = [ctypes.c_int32, ctypes.c_int32]
     L.dp_plan_order.argtypes = [ctypes.POINTER(Batch), ctypes.c_int32, c_i32p, c_i32p]
     _lib = L
     return L
@@ -847,6 +850,29 @@ def plan_placements(rec_off, rec, flags: int = 0) -> np.ndarray:
     if lib().dp_plan_placements(ctypes.byref(_batch(rec_off, rec)), flags, _p(place, c_i8p)) != 0:
         raise RuntimeError("dp_plan_placements failed")
     return place[:len(rec_off) - 1]
+
+
+def plan_footprints(rec_off, rec, flags: int = 0):
+    """Per-problem (lds_bytes, scratch_bytes) the same plan requests on each
+    problem's placement (dp_plan_footprints): the LDS footprint that buckets
+    it, and its HBM scratch; 0, 0 for a problem that is not launched."""
+    rec_off = np.ascontiguousarray(rec_off, np.int64)
+    rec = np.ascontiguousarray(rec if len(rec) else np.zeros(1, np.int32), np.int32)
+    n = len(rec_off) - 1
+    lds = np.zeros(max(n, 1), np.int32)
+    scratch = np.zeros(max(n, 1), np.int32)
+    if lib().dp_plan_footprints(ctypes.byref(_batch(rec_off, rec)), flags, _p(lds, c_i32p), _p(scratch, c_i32p)) != 0:
+        raise RuntimeError("dp_plan_footprints failed")
+    return lds[:n], scratch[:n]
+
+
+def lds_occupancy(lds_bytes: int, capped: bool = False) -> int:
+    """Workgroups of the one-wavefront kernel one CU holds at an LDS request
+    (dp_lds_occupancy: the HIP runtime's own figure; needs a GPU)."""
+    r = lib().dp_lds_occupancy(int(lds_bytes), int(bool(capped)))
+    if r < 0:
+        raise RuntimeError("dp_lds_occupancy failed")
+    return r
 
 
 def plan_order(rec_off, rec, flags: int = 0):

@@ -49,6 +49,12 @@ struct KernelArgs {
   // LDS limit): workgroup b works in scratch + scratch_off[b] (and in LDS)
   int32_t* scratch;
   const int64_t* scratch_off;
+  // One-wavefront launches (M_LDS): workgroup b keeps the CDCL-only arrays
+  // its LDS image leaves out (layout.hpp mode_evict) at scratch +
+  // lds_scratch_off + b * lds_scratch_stride (int32 words): equal regions, so
+  // there is no table to upload or to read before init
+  int64_t lds_scratch_off;
+  int64_t lds_scratch_stride;
   // diagnostic builds only (-DDP_STAMPS): per-problem phase cycle counts
   int64_t* stamps;
   // search trace (Tracer, search.go:173); null: not traced.  trace_cap words
@@ -75,7 +81,17 @@ constexpr int kQueueWords = 64;
 // Launch one workgroup per problem of order[0..n_blocks) with lds_bytes of
 // LDS: one wavefront (mode M_LDS) or a multi-wave workgroup (M_LDSG, M_SPLIT4,
 // M_SPLIT, M_HBM; layout.hpp mode_waves).
-hipError_t launch_solve(const KernelArgs& a, int mode, int n_blocks, int lds_bytes, hipStream_t stream);
+// dense (M_LDS only): the register-capped one-wavefront build, whose working
+// set is all in LDS; lds_bytes is then the launch's largest un-evicted
+// footprint (Layout::lds_bytes + Layout::bytes), else its largest lds_bytes.
+hipError_t launch_solve(const KernelArgs& a, int mode, int n_blocks, int lds_bytes, bool dense, hipStream_t stream);
+// Does a one-wavefront launch whose largest un-evicted footprint is
+// full_bytes take the register-capped build?  (The plan asks, so that the
+// launch's LDS request and the kernel's layout agree.)
+bool lds_dense(int full_bytes);
+// Workgroups of the one-wavefront kernel (either build) one CU holds at an
+// LDS request: hipOccupancyMaxActiveBlocksPerMultiprocessor; -1 on error.
+int lds_occupancy(int lds_bytes, bool dense);
 // Before a multi-wave launch (mode M_SPLIT / M_SPLIT4 / M_HBM) of n_items
 // items: the watch lists of its DP_FMT_I32 records above DEV_WATCH_VARS
 // variables into their scratch (watch_build.hip).  Other items are skipped.

@@ -4,9 +4,12 @@
 //
 // Two images of the same layout exist:
 //   IX = uint16_t : the LDS image.  Record arrays are narrowed to 16 bits on
-//                   load (every index of an eligible problem is < 65000), so a
-//                   ~240-variable catalog needs ~18 KiB and 8-9 problems fit
-//                   in one CU's 160 KiB of LDS.
+//                   load (every index of an eligible problem is < 65000).  The
+//                   one-wavefront image (M_LDS) also keeps the arrays only
+//                   Solve()'s decisions and learned rows use in an HBM
+//                   scratch (mode_evict below), so a ~240-variable catalog
+//                   needs 11-14.5 KB and 11 problems share one CU's 160 KiB
+//                   of LDS.
 //   IX = int32_t  : the HBM image for problems too large for LDS (or with
 //                   larger indices), solved by one multi-wave workgroup
 //                   (M_SPLIT / M_HBM below).
@@ -27,7 +30,8 @@ constexpr int32_t L_MAX = 64;
 
 // Three placements of the same working set (one template instantiation each):
 //   M_LDS   one wavefront per problem, the whole image narrowed to 16 bits and
-//           the whole working set in LDS (the batched small-catalog path)
+//           the working set in LDS (the batched small-catalog path), except
+//           the CDCL-only arrays, which live in an HBM scratch (mode_evict)
 //   M_SPLIT one workgroup of BIG_WAVES wavefronts per problem (large catalogs,
 //           e.g. config 4): the int32 image is read in place from HBM, the
 //           per-literal arrays live in an HBM scratch region, and the hot
@@ -49,6 +53,22 @@ static_assert((int)M_LDS == DP_PLACE_LDS && (int)M_SPLIT == DP_PLACE_SPLIT && (i
               "enum dp_place (include/deppy_hip.h) names the placements");
 // The 16-bit LDS image (M_LDS, M_LDSG): record and working set in LDS
 __host__ __device__ constexpr bool mode_n16(int mode) { return mode == M_LDS || mode == M_LDSG; }
+// The 16-bit image whose CDCL-only arrays (Layout: d_mark, l_off, l_lits) are
+// evicted from LDS to the problem's HBM scratch.  Only Solve()'s decisions,
+// its learned rows and their users touch them: on config 2 that is the 2-4%
+// of catalogs that are class B or UNSAT, while every catalog paid their
+// ~1.25 KB of LDS, one residency step (10 -> 11 per CU).  The kernel is
+// latency-bound per wave, so throughput follows residency.  The CDCL-only
+// bitsets (d_flip, seen, dset, fg: 128 bytes at 240 variables) stay in LDS:
+// conflict analysis updates them by atomics from one lane's serial loop, a
+// round trip to L2 each in HBM.  M_LDSG keeps everything in LDS: one
+// workgroup per CU, nothing to gain.  Nor does the register-capped
+// one-wavefront build (solve_lds_dense.hip): it runs launches whose
+// footprints let more than 16 problems share a CU, which registers bound and
+// LDS does not, so it keeps the whole working set in LDS (layout<M_LDS,
+// false>; its launch requests lds_bytes + bytes of the evicting layout, which
+// is that footprint exactly) and compiles without the scratch's addressing.
+__host__ __device__ constexpr bool mode_evict(int mode) { return mode == M_LDS; }
 #ifndef DP_BIG_WAVES
 #define DP_BIG_WAVES 8
 #endif
@@ -225,6 +245,24 @@ __host__ __device__ inline int64_t staged_words(const int32_t* h, bool narrow) {
   return (w + 3) & ~3LL;
 }
 
+// The evicted arrays' byte offsets in the problem's scratch (mode_evict), from
+// the variable count alone: the kernel holds the scratch's base and derives
+// an array's address where it uses it (three more 64-bit pointers, and the
+// per-lane addresses derived from them, held across the search loop cost
+// VGPRs; solve_kernel.hpp cd_at).
+struct CdclLayout {
+  int32_t d_mark, l_off, l_lits, bytes;
+};
+__host__ __device__ inline CdclLayout cdcl_layout(int32_t nv) {
+  CdclLayout C;
+  int32_t o = 0;
+  C.d_mark = o; o += (nv * 2 + 15) & ~15;
+  C.l_off = o;  o += ((L_MAX + 1) * 2 + 15) & ~15;
+  C.l_lits = o; o += ((nv + 64) * 2 + 15) & ~15;  // (lcap = nv + 64, layout_hc)
+  C.bytes = o;
+  return C;
+}
+
 // Byte offsets of every working-set array.  An offset is into the LDS
 // allocation when the mode places that array in LDS (in_lds below), else into
 // the problem's HBM scratch region.
@@ -237,6 +275,7 @@ struct Layout {
   int32_t trail;     // IX[nv] true literals in assignment order
   int32_t touched;   // IX[2nv] literals implied this round; analysis work list
   int32_t d_mark;    // IX[nv] trail length before each Solve() decision (its literal is trail[d_mark])
+                     //                                                            [HBM when mode_evict]
   int32_t imp;       // IX[2nv] lowest row implying literal l this round (all ones: none)
   int32_t d_flip;    // bits[nv] decision already flipped                          [LDS unless M_HBM]
   int32_t inS;       // bits[nv] guessed set (search.assumptions)                  [LDS unless M_HBM]
@@ -250,8 +289,8 @@ struct Layout {
   int32_t en2;       // bits[nid]                                                  [LDS unless M_HBM]
   int32_t crit;      // bits[nid] identities proven necessary by a core's model rotation [LDS unless M_HBM]
   int32_t idt;       // (M_LDS / M_LDSG) bits[nid] rows -> identities for the outputs (row_of)  [LDS]
-  int32_t l_off;     // IX[L_MAX+1] learned rows (rows nrows..)
-  int32_t l_lits;    // IX[lcap]
+  int32_t l_off;     // IX[L_MAX+1] learned rows (rows nrows..)                   [HBM when mode_evict]
+  int32_t l_lits;    // IX[lcap]                                                  [HBM when mode_evict]
   int32_t dq;        // IX[2*cap] deque of choices (list, idx)
   int32_t stk;       // IX[3*cap] guess stack (list, idx | G_SKIP, mark)
   int32_t wbuf;      // IX[wbuf] flattened work list (watch-list positions)       [LDS]
@@ -268,7 +307,7 @@ struct Layout {
   int32_t hc;        // slots (a power of two; 0 when the mode keeps rounds in HBM)
   int32_t wl;        // multi-wave, DP_FMT_I32 records: device-built w_off[2nv+2], then
                      // [ncl+nkl] int2 {row, row_info} entries  [HBM]
-  int32_t bytes;     // HBM scratch bytes (0 for M_LDS / M_LDSG)
+  int32_t bytes;     // HBM scratch bytes (0 for M_LDSG; M_LDS: the evicted CDCL-only arrays)
   int32_t lds_bytes; // LDS bytes
   int32_t cap, lcap;
 };
@@ -293,8 +332,9 @@ __host__ __device__ inline int32_t round_slots(int32_t nv) {
   return c;
 }
 
-template <int MODE>
+template <int MODE, bool EV = mode_evict(MODE)>
 __host__ __device__ inline Layout layout_hc(const int32_t* h, int32_t hc) {
+  static_assert(!EV || mode_evict(MODE), "only an evicting mode has the evicting layout");
   constexpr bool N16 = mode_n16(MODE);
   using IX = typename std::conditional<N16, uint16_t, int32_t>::type;
   Layout L;
@@ -303,7 +343,12 @@ __host__ __device__ inline Layout layout_hc(const int32_t* h, int32_t hc) {
   const int32_t ix = (int32_t)sizeof(IX);
   int32_t og = 0, ol = 0;
   // every array 16-byte aligned; `hot` arrays go to LDS unless M_HBM, the
-  // per-literal arrays to LDS only in M_LDS / M_LDSG, the work lists always to LDS
+  // per-literal arrays to LDS only in M_LDS / M_LDSG, the work lists always to
+  // LDS; the CDCL-only arrays leave LDS for the scratch when the mode evicts
+  // them (cdcl_layout)
+  static_assert(!EV || N16, "cdcl_layout is the 16-bit image's");
+  const CdclLayout C = cdcl_layout(nv);
+  enum { COLD = 0, HOT = 1, WORK = 2 };
   auto take = [&](int32_t nbytes, int kind) {
     const bool lds = N16 || kind == 2 || (kind == 1 && (MODE == M_SPLIT || MODE == M_SPLIT4));
     int32_t& o = lds ? ol : og;
@@ -311,7 +356,6 @@ __host__ __device__ inline Layout layout_hc(const int32_t* h, int32_t hc) {
     o += (nbytes + 15) & ~15;
     return at;
   };
-  enum { COLD = 0, HOT = 1, WORK = 2 };
   L.cap = h[DP_H_NA] + h[DP_H_NCH] + 2;
   L.lcap = nv + 64;
   const ImgLayout X = img_layout(h);
@@ -353,14 +397,14 @@ __host__ __device__ inline Layout layout_hc(const int32_t* h, int32_t hc) {
   L.rs = take(nv * ix, COLD);
   L.trail = take(nv * ix, COLD);
   L.touched = take(2 * nv * ix, COLD);
-  L.d_mark = take(nv * ix, COLD);
+  L.d_mark = EV ? C.d_mark : take(nv * ix, COLD);
   L.imp = take(2 * nv * (N16 ? 2 : 4), COLD);
-  L.l_off = take((L_MAX + 1) * ix, COLD);
-  L.l_lits = take(L.lcap * ix, COLD);
+  L.l_off = EV ? C.l_off : take((L_MAX + 1) * ix, COLD);
+  L.l_lits = EV ? C.l_lits : take(L.lcap * ix, COLD);
   L.dq = take(2 * L.cap * ix, COLD);
   L.stk = take(3 * L.cap * ix, COLD);
   L.wl = !N16 && h[DP_H_FMT] == DP_FMT_I32 ? take((2 * nv + 2) * 4 + (h[DP_H_NCL] + h[DP_H_NKL]) * 8, COLD) : 0;
-  L.bytes = og;
+  L.bytes = EV ? C.bytes : og;
   L.lds_bytes = ol;
   return L;
 }
@@ -371,9 +415,9 @@ __host__ __device__ inline Layout layout_hc(const int32_t* h, int32_t hc) {
 // not a formula beside it: round 5 added an identity bitset (crit) that a
 // hand-written budget left out, and every OLM-scale catalog fell to M_HBM.
 constexpr int32_t kLdsLimitBytes = 160 * 1024;  // LDS per CU on gfx950
-template <int MODE>
+template <int MODE, bool EV = mode_evict(MODE)>
 __host__ __device__ inline Layout layout(const int32_t* h) {
-  if (!mode_lds_rounds(MODE)) return layout_hc<MODE>(h, 0);
+  if (!mode_lds_rounds(MODE)) return layout_hc<MODE, EV>(h, 0);
   int32_t hc = round_slots(h[DP_H_NV]);
   Layout L = layout_hc<MODE>(h, hc);
   while (hc > 64 && L.lds_bytes > kLdsLimitBytes) L = layout_hc<MODE>(h, hc >>= 1);

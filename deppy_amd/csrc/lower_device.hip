@@ -519,7 +519,9 @@ __global__ void __launch_bounds__(DL_T) lower_kernel(DlArgs a) {
   h[DP_H_NCHL] = nchl;
   h[DP_H_WORDS] = DP_H_SIZE + (nc + 1) + ncl + nc + (nk + 1) + nkl + 2 * nk + (nv + 1) + (nch + 1) + nchl + na;
   // one wavefront per problem (placement.hpp lds_image)
-  if (!fits16_dev(h) || (int64_t)dp::layout<dp::M_LDS>(h).lds_bytes > a.group_above) return give_up();
+  // (the whole working set, LDS and scratch, as placement.hpp one_wave compares it)
+  const dp::Layout wl = dp::layout<dp::M_LDS>(h);
+  if (!fits16_dev(h) || (int64_t)wl.lds_bytes + wl.bytes > a.group_above) return give_up();
   auto put_header = [&]() {
     for (int i = lane; i < DL_SLOT; i += DL_T) S.rec[i] = 0u;
     __syncthreads();

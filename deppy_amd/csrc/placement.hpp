@@ -30,8 +30,14 @@ inline int64_t group_above() {
 
 // Does the record (header h, well formed) run one wavefront per problem on
 // its 16-bit LDS image (without DP_OPT_FORCE_* flags)?
+// (The footprint is the whole working set, the arrays M_LDS keeps in HBM
+// scratch included -- layout.hpp mode_evict -- so evicting them moves no
+// catalog between placements: config 5's largest one-wavefront catalogs are
+// its slowest.)
 inline bool one_wave(const int32_t* h) {
-  return fits16(h) && (int64_t)layout<M_LDS>(h).lds_bytes <= group_above();
+  if (!fits16(h)) return false;
+  const Layout L = layout<M_LDS>(h);
+  return (int64_t)L.lds_bytes + L.bytes <= group_above();
 }
 
 // The all-LDS multi-wave placement (M_LDSG) for 16-bit records past

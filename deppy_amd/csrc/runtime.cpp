@@ -66,7 +66,13 @@ constexpr int64_t kDefaultBudget = 1 << 16;        // BCP invocations per proble
 // one after another on its stream, each as long as its slowest problem:
 // fine buckets split config 2 into 2-3 launches and it fell from 22.1M to
 // 14.3M res/s (profiles/r03_buckets_ab.jsonl).  Residency has to come from
-// smaller footprints, not from more launches.
+// smaller footprints, not from more launches: the one-wavefront image keeps
+// the arrays only Solve()'s decisions and learned rows use in HBM scratch
+// (layout.hpp mode_evict), which takes config 2's one launch from a
+// 16,064-byte request (10 per CU) to 14,576 (11 per CU); the measured
+// effect is in profiles/evict_ab.txt.  (That launch was one launch under
+// DEPPY_CEILINGS=fine too: the join rule below compares whole per-CU counts,
+// 10 >= 0.5 * 16, so every finer bucket joined it.)
 constexpr int kNBuckets = 16;
 struct Ceilings {
   int c[kNBuckets];
@@ -159,6 +165,8 @@ struct Launch {
   int first, count, mode, lds;
   bool dev_lists;  // holds DP_FMT_I32 records above DEV_WATCH_VARS variables, whose watch lists the
                    // grid-wide passes build (watch_build.hip); copied as they lie or by stage_one alike
+  bool dense = false;  // M_LDS: the register-capped build, whole working set in LDS (kernel_api.hpp lds_dense);
+                       // lds is then the launch's largest lds + scratch
 };
 
 // What the plan needs of one record, from its header alone (one cache line
@@ -173,6 +181,7 @@ struct Head {
   int32_t lds, inst_words, nid;
   int64_t sw, rec_bytes;
   uint8_t cls;    // cost class of a one-wavefront problem: its anchors (plan_chunk's dispatch order)
+  int32_t scratch;  // M_LDS: HBM scratch bytes (the evicted CDCL-only state, layout.hpp mode_evict)
 };
 
 // One block of plan_chunk's passes: its sums, then (after the scan) its
@@ -183,6 +192,8 @@ struct PlanBlock {
   int64_t img = 0, inst = 0, core = 0, rbytes = 0, other = 0;
   int32_t ndirect = 0, nother = 0, nok = 0;
   int32_t bcount[kNBuckets] = {}, bmax[kNBuckets] = {};
+  int32_t smax = 0;  // largest one-wavefront scratch (bytes)
+  int32_t bfull[kNBuckets] = {};  // per bucket, the largest un-evicted footprint (lds + scratch)
 };
 
 struct Plan {
@@ -194,6 +205,13 @@ struct Plan {
   std::vector<Launch> launches;   // in enqueue order (multi-wave first)
   int big_base = 0;               // first order index of the multi-wave problems
   std::vector<int64_t> scratch_off;  // [order.size() - big_base] int32-word offsets
+  // One-wavefront problems (the CDCL-only arrays their LDS image leaves out,
+  // layout.hpp mode_evict): order index t >= lds_first works in the scratch at
+  // word lds_scratch_base + (t - lds_first) * lds_scratch_stride -- one region
+  // of the chunk's largest per problem, so the plan writes and the chunk
+  // uploads no table for them (a table of offsets per problem was measured:
+  // config 6 host to host 51.5M -> 44.8M res/s, profiles/evict_ab.txt)
+  int64_t lds_scratch_base = 0, lds_scratch_stride = 0, lds_first = 0;
   int64_t scratch_words = 0;
   std::vector<int32_t> skip;      // local problems not launched (-> DP_ERROR)
   std::vector<int32_t> skip_flags; // their dp_flag (DP_F_TOO_LARGE / DP_F_MALFORMED)
@@ -240,8 +258,10 @@ void read_head(Head& H, const int32_t* h, int64_t avail, int32_t opt_flags, bool
   bool nar = false;
   if (dp::fits16(h)) {
     if (!forced_of(opt_flags)) {
-      H.lds = layout<M_LDS>(h).lds_bytes;
-      nar = H.lds <= dp::group_above();
+      const Layout Y = layout<M_LDS>(h);
+      H.lds = Y.lds_bytes;
+      H.scratch = Y.bytes;
+      nar = (int64_t)Y.lds_bytes + Y.bytes <= dp::group_above();  // (one_wave: the whole working set)
     }
     if (!nar && (!forced_of(opt_flags) || (opt_flags & DP_OPT_FORCE_LDSG)) && dp::ldsg_fits(h)) {
       if (opt_flags & DP_OPT_FORCE_LDSG) {
@@ -306,6 +326,7 @@ void plan_chunk(Plan& P, const int32_t* rec, const int64_t* rec_off, int32_t p0,
   P.scratch_words = P.core_cap = P.rec_bytes = P.other_words = 0;
   P.n_direct = 0;
   P.big_base = 0;
+  P.lds_scratch_base = P.lds_scratch_stride = P.lds_first = 0;
   Head* head = P.head.data();
   // Three passes over blocks of kPlanBlock problems (on the pool when there
   // are several blocks; the per-problem work is a header cache miss and its
@@ -373,6 +394,8 @@ void plan_chunk(Plan& P, const int32_t* rec, const int64_t* rec_off, int32_t p0,
       if (H.place == M_LDS) {
         B.bcount[H.bucket]++;
         B.bmax[H.bucket] = std::max(B.bmax[H.bucket], H.lds);
+        B.smax = std::max(B.smax, H.scratch);
+        B.bfull[H.bucket] = std::max(B.bfull[H.bucket], H.lds + H.scratch);
       } else {
         B.nother++;
       }
@@ -385,8 +408,9 @@ void plan_chunk(Plan& P, const int32_t* rec, const int64_t* rec_off, int32_t p0,
     }
   });
   for (auto& v : P.big) v.clear();
-  int32_t bcount[kNBuckets] = {}, bmax[kNBuckets] = {};
+  int32_t bcount[kNBuckets] = {}, bmax[kNBuckets] = {}, bfull[kNBuckets] = {};
   int64_t img = 0, inst = 0;
+  int32_t smax = 0;
   bool others = false;
   for (int32_t b = 0; b < nblk; ++b) {  // the scan
     PlanBlock& B = P.blk[(size_t)b];
@@ -400,9 +424,11 @@ void plan_chunk(Plan& P, const int32_t* rec, const int64_t* rec_off, int32_t p0,
     P.core_cap += B.core;
     P.rec_bytes += B.rbytes;
     others |= B.nother > 0;
+    smax = std::max(smax, B.smax);
     for (int k = 0; k < kNBuckets; ++k) {
       bcount[k] += B.bcount[k];
       bmax[k] = std::max(bmax[k], B.bmax[k]);
+      bfull[k] = std::max(bfull[k], B.bfull[k]);
     }
   }
   P.dev_off.resize((size_t)n);
@@ -492,6 +518,7 @@ void plan_chunk(Plan& P, const int32_t* rec, const int64_t* rec_off, int32_t p0,
   int group_of[kNBuckets];
   Launch bl[kNBuckets];
   int64_t gsize[kNBuckets] = {};
+  int32_t gfull[kNBuckets] = {};
   int ng = 0;
   for (int k = kNBuckets - 1; k >= 0; --k) {
     if (!bcount[k]) continue;
@@ -501,7 +528,16 @@ void plan_chunk(Plan& P, const int32_t* rec, const int64_t* rec_off, int32_t p0,
     if (!join) bl[ng++] = Launch{0, 0, M_LDS, bmax[k]};
     group_of[k] = ng - 1;
     gsize[ng - 1] += bcount[k];
+    gfull[ng - 1] = std::max(gfull[ng - 1], bfull[k]);
   }
+  // A launch that LDS does not bound (more than 16 problems per CU even with
+  // everything in LDS) takes the register-capped build, which evicts nothing:
+  // it requests the un-evicted footprint, as it always did.
+  for (int g = 0; g < ng; ++g)
+    if (dp::lds_dense(gfull[g])) {
+      bl[g].dense = true;
+      bl[g].lds = gfull[g];
+    }
   // the bucket launches, the most problems first; members in problem order,
   // then each launch's members by LPT
   int ix[kNBuckets];
@@ -515,6 +551,14 @@ void plan_chunk(Plan& P, const int32_t* rec, const int64_t* rec_off, int32_t p0,
     o += gsize[g];
   }
   P.order.resize((size_t)o);
+  // One-wavefront scratch, after the multi-wave regions: touched only by the
+  // problems that reach a conflict under Solve() or a refutation.
+  if (ng > 0) {
+    P.lds_first = bl[ix[0]].first;
+    P.lds_scratch_stride = ((int64_t)smax + 15) / 16 * 4;  // int32 words, 16-byte aligned
+    P.lds_scratch_base = P.scratch_words;
+    P.scratch_words += (o - P.lds_first) * P.lds_scratch_stride;
+  }
   // XCD-contiguous order for one-wavefront launches up to this LDS request
   // (DEPPY_XCD_ORDER, bytes; 0: longest record first everywhere).  Measured
   // on one box against LPT: config 2 host to host 18.4-18.5M -> 20.3-20.6M
@@ -1053,6 +1097,7 @@ struct FastLane {
   hipStream_t s = nullptr;
   hipEvent_t done = nullptr;
   Buf h_in{nullptr, 0, true}, h_out{nullptr, 0, true};
+  Buf scratch;  // device memory: the problems' CDCL-only state (layout.hpp mode_evict)
   Plan plan;
   std::vector<uint8_t> bad;
 };
@@ -1230,6 +1275,8 @@ int enqueue_launches(dp_ctx* ctx, const Plan& P, const dp::KernelArgs& base, hip
     }
     dp::KernelArgs a = base;
     a.items = base.items + L.first;
+    a.lds_scratch_off = P.lds_scratch_base + (L.first - P.lds_first) * P.lds_scratch_stride;
+    a.lds_scratch_stride = P.lds_scratch_stride;
     if (L.mode != dp::M_LDS) {
       a.scratch_off = base.scratch_off + (L.first - P.big_base);
       a.queue = no_queue ? nullptr : base.scratch + q;
@@ -1239,7 +1286,7 @@ int enqueue_launches(dp_ctx* ctx, const Plan& P, const dp::KernelArgs& base, hip
       ++q;
       if (L.dev_lists) HIP_OK(dp::launch_watch_build(a, L.mode, L.count, s));
     }
-    HIP_OK(dp::launch_solve(a, L.mode, L.count, L.lds, t));
+    HIP_OK(dp::launch_solve(a, L.mode, L.count, L.lds, L.dense, t));
     if (t != s) {
       HIP_OK(hipEventRecord(sp->fin[nf], t));
       HIP_OK(hipStreamWaitEvent(s, sp->fin[nf], 0));
@@ -1695,13 +1742,16 @@ int fast_solve(dp_ctx* ctx, Device& D, const dp_batch* b, dp_result* res) {
   if (hipSetDevice(D.ordinal) != hipSuccess) return 1;
   const InLayout il = in_layout(P);
   const OutLayout ol = out_layout(P);
-  if (F.h_in.reserve(il.end) != hipSuccess || F.h_out.reserve(ol.end) != hipSuccess) return 1;
+  if (F.h_in.reserve(il.end) != hipSuccess || F.h_out.reserve(ol.end) != hipSuccess ||
+      F.scratch.reserve((size_t)std::max<int64_t>(P.scratch_words, 1) * 4) != hipSuccess)
+    return 1;
   int32_t* img = at<int32_t>(F.h_in.p, il.img);
   for (int32_t i = 0; i < n; ++i)
     if (!dp::stage_one(P, b->rec, b->rec_off, 0, i, img, true)) F.bad[(size_t)i] = 1;
   fill_in_tables(P, il, F.h_in.p);
   *at<int32_t>(F.h_out.p, ol.pool_len) = 0;
-  dp::KernelArgs a = kernel_args(il, ol, F.h_in.dev, F.h_out.dev, nullptr, ctx->budget);
+  dp::KernelArgs a = kernel_args(il, ol, F.h_in.dev, F.h_out.dev, reinterpret_cast<int32_t*>(F.scratch.p),
+                                 ctx->budget);
   dp_stats st{};
   if (enqueue_launches(ctx, P, a, F.s, st) || hipEventRecord(F.done, F.s) != hipSuccess) return api_fail(ctx);
   // poll: a sleeping wait costs more than the solve of one small catalog
@@ -1878,6 +1928,7 @@ void dp_destroy(dp_ctx* ctx) {
     if (D.fast.s) (void)hipStreamSynchronize(D.fast.s);
     D.fast.h_in.release();
     D.fast.h_out.release();
+    D.fast.scratch.release();
     if (D.fast.done) (void)hipEventDestroy(D.fast.done);
     if (D.fast.s) (void)hipStreamDestroy(D.fast.s);
   }
@@ -1953,6 +2004,38 @@ int dp_plan_placements(const dp_batch* b, int32_t opt_flags, int8_t* place) {
   for (int32_t i = 0; i < b->n_problems; ++i) place[i] = (int8_t)P.head[(size_t)i].place;
   return 0;
 }
+
+int dp_plan_footprints(const dp_batch* b, int32_t opt_flags, int32_t* lds_bytes, int32_t* scratch_bytes) {
+  if (!b || !lds_bytes || !scratch_bytes || b->n_problems < 0 || (b->n_problems > 0 && (!b->rec || !b->rec_off)))
+    return -1;
+  static thread_local Plan P;
+  dp::plan_chunk(P, b->rec, b->rec_off, 0, b->n_problems, opt_flags, nullptr, &dp::host_pool());
+  for (int32_t i = 0; i < b->n_problems; ++i) {
+    const auto& H = P.head[(size_t)i];
+    const int32_t* h = b->rec + b->rec_off[i];
+    dp::Layout Y{};
+    switch (H.place) {  // (the layouts plan_chunk sizes the launches and the scratch by)
+      case dp::M_LDS: Y.lds_bytes = H.lds; Y.bytes = H.scratch; break;
+      case dp::M_LDSG: Y = dp::layout<dp::M_LDSG>(h); break;
+      case dp::M_SPLIT: Y = dp::layout<dp::M_SPLIT>(h); break;
+      case dp::M_SPLIT4: Y = dp::layout<dp::M_SPLIT4>(h); break;
+      case dp::M_HBM: Y = dp::layout<dp::M_HBM>(h); break;
+      default: break;
+    }
+    lds_bytes[i] = Y.lds_bytes;
+    scratch_bytes[i] = Y.bytes;
+  }
+  for (const auto& L : P.launches)  // the register-capped build keeps the whole working set in LDS
+    if (L.mode == dp::M_LDS && L.dense)
+      for (int t = L.first; t < L.first + L.count; ++t) {
+        const int32_t i = P.order[(size_t)t];
+        lds_bytes[i] += scratch_bytes[i];
+        scratch_bytes[i] = 0;
+      }
+  return 0;
+}
+
+int dp_lds_occupancy(int32_t lds_bytes, int32_t capped) { return dp::lds_occupancy(lds_bytes, capped != 0); }
 
 // ---- host-to-host pipeline ----
 

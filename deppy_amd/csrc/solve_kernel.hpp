@@ -187,6 +187,38 @@ struct Group {
     if constexpr (MODE != M_HBM) return *p;
     else return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
+  // The one-wavefront image keeps its CDCL-only arrays (layout.hpp
+  // mode_evict: d_mark, l_off, l_lits) in the problem's HBM scratch, under
+  // M_HBM's convention for the same arrays: the wavefront's stores are
+  // drained (cd_drain) before another lane reads them.  A catalog that never
+  // reaches a conflict touches none of them: l_off[0] is initialised at the
+  // first analysis (cd_ready), which every read of l_off follows.
+  // (not in the register-capped build, MINW > 1: layout.hpp mode_evict)
+  static constexpr bool EV = mode_evict(MODE) && MINW == 1;
+  __device__ __forceinline__ static void cd_drain() {
+    if constexpr (EV) __builtin_amdgcn_s_waitcnt(0);  // vmcnt(0) expcnt(0) lgkmcnt(0)
+  }
+  bool cd_ready;
+  // The evicted arrays are reached from the scratch's base where they are
+  // used (layout.hpp cdcl_layout), through a value the compiler cannot trace
+  // back: otherwise it hoists the per-lane 64-bit addresses of these rare
+  // paths out of the search loop and holds them in VGPRs across it (measured
+  // with seven arrays evicted as pointer members: 117 VGPRs against the
+  // parent's 105; with this, 108).  The address space stays known, so every
+  // access is global_*, never flat_*.
+  char* cdb;
+  template <class T>
+  __device__ __forceinline__ T* cd_at(int32_t off) const {
+    uint64_t x = reinterpret_cast<uint64_t>(cdb);
+    asm volatile("" : "+s"(x));
+    using gchar = __attribute__((address_space(1))) char;
+    return (T*)((gchar*)x + off);  // (C-style: a cast out of the global address space)
+  }
+#define DP_CD_ARRAY(T, name)                                        \
+  __device__ __forceinline__ T* a_##name() const {                  \
+    if constexpr (EV) return cd_at<T>(cdcl_layout(nv).name);        \
+    else return name;                                               \
+  }
 
   // ---- record views ----
   int nv, nc, nk, nid, nrows, nbv, nbi, na, nch, ncl, nkl, nchl;
@@ -239,6 +271,11 @@ struct Group {
   IX *reason, *rs, *trail, *touched, *d_mark, *l_off, *l_lits, *dq, *stk;
   IMP* imp;  // imp[l] = lowest row implying literal l this round
   uint32_t *d_flip, *inS, *extra, *seen, *model, *used, *en, *en2, *crit, *dset, *fg;
+  // (the CDCL-only arrays are used through a_<name>(), see cd_at)
+  DP_CD_ARRAY(IX, d_mark)
+  DP_CD_ARRAY(IX, l_off)
+  DP_CD_ARRAY(IX, l_lits)
+#undef DP_CD_ARRAY
   IX *wbuf, *cardq;
   int32_t* scal;
   // LDS round state (mode_lds_rounds; layout.hpp Layout::hkey..fr)
@@ -421,7 +458,7 @@ struct Group {
 #ifdef DP_STAMPS
     const int64_t ti0 = stamp();
 #endif
-    const Layout L = layout<MODE>(h);
+    const Layout L = layout<MODE, EV>(h);
     const dp_rec_layout R = rec_layout(h);
     const ImgLayout X = img_layout(h);
     // the group primitives' LDS words first (the decode's g_any uses them)
@@ -527,12 +564,13 @@ struct Group {
     dthr = nrows + L_MAX;
     char* hot = MODE == M_HBM ? hbm : lds;  // val and the bitsets
     char* cold = N16 ? lds : hbm;           // per-literal arrays
+    cdb = hbm;  // (mode_evict: the CDCL-only arrays, a_<name>())
     val = reinterpret_cast<int8_t*>(hot + L.val);
     reason = reinterpret_cast<IX*>(cold + L.reason);
     rs = reinterpret_cast<IX*>(cold + L.rs);
     trail = reinterpret_cast<IX*>(cold + L.trail);
     touched = reinterpret_cast<IX*>(cold + L.touched);
-    d_mark = reinterpret_cast<IX*>(cold + L.d_mark);
+    d_mark = EV ? nullptr : reinterpret_cast<IX*>(cold + L.d_mark);  // (EV: a_d_mark(); a direct use faults)
     imp = reinterpret_cast<IMP*>(cold + L.imp);
     w8 = nullptr;
     d_flip = reinterpret_cast<uint32_t*>(hot + L.d_flip);
@@ -547,8 +585,8 @@ struct Group {
     en2 = reinterpret_cast<uint32_t*>(hot + L.en2);
     crit = reinterpret_cast<uint32_t*>(hot + L.crit);
     idt = reinterpret_cast<uint32_t*>(lds + L.idt);
-    l_off = reinterpret_cast<IX*>(cold + L.l_off);
-    l_lits = reinterpret_cast<IX*>(cold + L.l_lits);
+    l_off = EV ? nullptr : reinterpret_cast<IX*>(cold + L.l_off);
+    l_lits = EV ? nullptr : reinterpret_cast<IX*>(cold + L.l_lits);
     dq = reinterpret_cast<IX*>(cold + L.dq);
     stk = reinterpret_cast<IX*>(cold + L.stk);
     wbuf = reinterpret_cast<IX*>(lds + L.wbuf);
@@ -631,9 +669,10 @@ struct Group {
     }
     for (int i = tid; i < mode_nscal(MODE); i += NT) scal[i] = 0;
     if (tid == 0) {  // (after the zeroing in program order: both are wavefront 0's stores)
-      l_off[0] = 0;
+      if constexpr (!EV) l_off[0] = 0;
       scal[S_POSROWS] = h[DP_H_NVU] > 0;
     }
+    cd_ready = !EV;  // (evicted: no global access before the first analysis, see analyze)
     gsync();
     return true;
   }
@@ -1302,7 +1341,8 @@ struct Group {
     }
     if (r < nc) return eval_clause(r, clause_lits, clause_off[r], clause_off[r + 1], crow);
     const int j = r - nrows;
-    return eval_clause(r, l_lits, DP_CHK((int)l_off[j], 0, lcap + 1, 33), DP_CHK((int)l_off[j + 1], 0, lcap + 1, 34), crow);
+    const IX* lo = a_l_off();
+    return eval_clause(r, a_l_lits(), DP_CHK((int)lo[j], 0, lcap + 1, 33), DP_CHK((int)lo[j + 1], 0, lcap + 1, 34), crow);
   }
 
   // an AtMost row in one lane (several wavefronts, AtMost queue full)
@@ -1880,17 +1920,20 @@ struct Group {
   __device__ __forceinline__ void ante_serial(int r, int u, int bound) {
     r = DP_CHK(r, 0, nrows + nl, 15);
     if (r < nc || r >= nrows) {
-      const IX* lits = clause_lits;
-      int a, b;
-      if (r < nc) { a = clause_off[r]; b = clause_off[r + 1]; set_bit_atomic(used, row_key(r)); }
-      else {
-        lits = l_lits;
-        a = DP_CHK((int)l_off[r - nrows], 0, lcap + 1, 35);
-        b = DP_CHK((int)l_off[r - nrows + 1], 0, lcap + 1, 36);
-      }
-      for (int j = a; j < b; ++j) {
-        const int v = (int)lits[j] >> 1;
-        if (v != u) mark_push(v);
+      // (a call per array: a pointer chosen between clause_lits in LDS and
+      // l_lits in HBM would make every access of the loop a flat one)
+      auto mark_row = [&](const IX* lits, int a, int b) {
+        for (int j = a; j < b; ++j) {
+          const int v = (int)lits[j] >> 1;
+          if (v != u) mark_push(v);
+        }
+      };
+      if (r < nc) {
+        set_bit_atomic(used, row_key(r));
+        mark_row(clause_lits, clause_off[r], clause_off[r + 1]);
+      } else {
+        const IX* lo = a_l_off();
+        mark_row(a_l_lits(), DP_CHK((int)lo[r - nrows], 0, lcap + 1, 35), DP_CHK((int)lo[r - nrows + 1], 0, lcap + 1, 36));
       }
     } else {
       const int k = r - nc;
@@ -1916,6 +1959,13 @@ struct Group {
   }
   __device__ __forceinline__ void analyze_() {
 #endif
+    if constexpr (EV) {
+      if (!cd_ready) {  // the first analysis of this problem: its first global access after init
+        if (tid == 0) a_l_off()[0] = 0;
+        cd_ready = true;
+        cd_drain();
+      }
+    }
     gsync();
     if (tid == 0) {
       scal[S_NWORK] = 0;
@@ -2071,7 +2121,7 @@ struct Group {
 
   // Solve() decision i's literal: the trail entry at its mark, unflipped
   __device__ __forceinline__ int dlit(int i) const {
-    return (int)trail[(int)d_mark[i]] ^ (int)getb(d_flip, i);
+    return (int)trail[(int)a_d_mark()[i]] ^ (int)getb(d_flip, i);
   }
 
   __device__ __forceinline__ int dpll() {
@@ -2084,7 +2134,7 @@ struct Group {
         if (l < 0) { save_model(); r = RS_SAT; break; }
         if (++steps > budget) { budget_hit = true; r = RS_BUDGET; break; }
         if (tid == 0) {
-          d_mark[nd] = enc(tlen);  // the decision's literal is trail[d_mark[nd]]
+          a_d_mark()[nd] = enc(tlen);  // the decision's literal is trail[d_mark[nd]]
           d_flip[nd >> 5] &= ~(1u << (nd & 31));
         }
         assign_one(l, R_DEC, nd);
@@ -2094,6 +2144,7 @@ struct Group {
       if (propagate() >= 0) { decide = true; continue; }
       decide = false;
       clear_bits(dset, nd);
+      cd_drain();  // (the decisions' d_mark stores, read below)
       analyze();
       // h = highest decision reached, b = the next one below (or -1)
       int h = -1, b = -1, n = 0;
@@ -2108,7 +2159,7 @@ struct Group {
       for (int wi = 0; wi < bits_words(nd); ++wi) n += __popc(ld_bits(&dset[wi]));
       if (h < 0) { r = RS_UNSAT; break; }
       if (++steps > budget) { budget_hit = true; r = RS_BUDGET; break; }
-      const int lat = DP_CHK((int)l_off[nl], 0, lcap + 1, 26);
+      const int lat = DP_CHK((int)a_l_off()[nl], 0, lcap + 1, 26);
       if (nl < L_MAX && lat + n <= lcap) {
         // learned row: the negated decisions it met
         int run = lat;
@@ -2116,21 +2167,22 @@ struct Group {
           const int i = base + tid;
           const bool in = i < nd && ((ld_bits(&dset[i >> 5]) >> (i & 31)) & 1u);
           const int at = claim(in, run);
-          if (in) l_lits[DP_CHK(at, 0, lcap, 27)] = enc(dlit(i) ^ 1);
+          if (in) a_l_lits()[DP_CHK(at, 0, lcap, 27)] = enc(dlit(i) ^ 1);
         }
         claim_end(run);
-        if (tid == 0) l_off[nl + 1] = enc(run);
+        if (tid == 0) a_l_off()[nl + 1] = enc(run);
         ++nl;
+        cd_drain();
         gsync();
         const int lh = dlit(h);
         nd = b + 1;
-        truncate_to(DP_CHK((int)d_mark[nd], 0, nv + 1, 24));
+        truncate_to(DP_CHK((int)a_d_mark()[nd], 0, nv + 1, 24));
         assign_one(lh ^ 1, nrows + nl - 1, -1);
       } else {
         while (nd > 0 && getb(d_flip, nd - 1)) --nd;
         if (nd == 0) { r = RS_UNSAT; break; }
         const int lf = dlit(nd - 1);  // before its flip bit is set
-        truncate_to(DP_CHK((int)d_mark[nd - 1], 0, nv + 1, 25));
+        truncate_to(DP_CHK((int)a_d_mark()[nd - 1], 0, nv + 1, 25));
         if (tid == 0) d_flip[(nd - 1) >> 5] |= 1u << ((nd - 1) & 31);
         gsync();
         assign_one(lf ^ 1, R_DEC, nd - 1);
@@ -2294,18 +2346,19 @@ struct Group {
       int n = 0;
       for (int wi = tid; wi < nbv; wi += NT) n += __popc(ld_bits(&fg[wi]));
       n = g_sum(n);
-      const int lat = l_off[nl];
+      const int lat = a_l_off()[nl];
       if (nl < L_MAX && lat + n <= lcap) {
         int run = lat;
         for (int b = 0; b < nv; b += NT) {
           const int v = b + tid;
           const bool in = v < nv && ((ld_bits(&fg[v >> 5]) >> (v & 31)) & 1u);
           const int at = claim(in, run);
-          if (in) l_lits[at] = enc(2 * v + 1);
+          if (in) a_l_lits()[at] = enc(2 * v + 1);
         }
         claim_end(run);
-        if (tid == 0) l_off[nl + 1] = enc(run);
+        if (tid == 0) a_l_off()[nl + 1] = enc(run);
         ++nl;
+        cd_drain();
         gsync();
       }
     }
@@ -2764,12 +2817,14 @@ struct Group {
 #define DP_LDS_MIN_WAVES 5
 #endif
 // (MINW: minimum waves per SIMD the kernel is compiled for.  The one-wavefront
-// kernel has two builds: unbounded (105 VGPRs: 4 waves per SIMD, 16 per CU)
-// and DP_LDS_MIN_WAVES = 5 (94 VGPRs: 20 per CU), neither with a spill
+// kernel has two builds: unbounded (4 waves per SIMD, 16 per CU) and
+// DP_LDS_MIN_WAVES = 5 (at most 102 VGPRs: 20 per CU), neither with a spill
+// (the counts: DESIGN.md 5.4)
 // (tests/test_placement.py reads the code objects).  The capped build only
 // pays where LDS would let more than 16 problems share a CU (small
-// catalogs, config 3); launch_solve picks the build per launch by
-// footprint.  Before round 6 the whole-wave reductions were __shfl_xor
+// catalogs, config 3); the plan picks the build per launch by footprint
+// (kernel_api.hpp lds_dense), and the capped build keeps the whole working
+// set in LDS (layout.hpp mode_evict).  Before round 6 the whole-wave reductions were __shfl_xor
 // butterflies whose ds_bpermute addresses the compiler kept live across the
 // search loop: 163 VGPRs unbounded, and 13 spilled at a 128 cap.  A cap of 6
 // waves (80 VGPRs) spills 11.)
@@ -2808,7 +2863,9 @@ __device__ __forceinline__ void solve_item(const KernelArgs& a, int k, int4* lds
   const int pid = it.pid;
   const int32_t* grec = a.rec + it.rec_off;
   Group<MODE, MINW> W;
-  char* hbm = mode_n16(MODE) ? nullptr : reinterpret_cast<char*>(a.scratch + a.scratch_off[k]);
+  char* hbm = nullptr;  // (M_LDSG has no scratch)
+  if constexpr (Group<MODE, MINW>::EV) hbm = reinterpret_cast<char*>(a.scratch + a.lds_scratch_off + k * a.lds_scratch_stride);
+  else if constexpr (!mode_n16(MODE)) hbm = reinterpret_cast<char*>(a.scratch + a.scratch_off[k]);
   if (!W.init(reinterpret_cast<char*>(lds4), hbm, grec)) {
     if (threadIdx.x == 0) {  // a malformed record: no solve (dp_rec_validate's verdict)
       put_out(a.out + pid, DP_ERROR, DP_F_MALFORMED, 0, 0, 0, 0);
@@ -2959,6 +3016,13 @@ inline bool debug_grid() {
     hipLaunchKernelGGL((solve_kernel<MODE, MINW>), dim3((unsigned)grid), dim3(64 * mode_waves(MODE)), \
                        (size_t)lds_bytes, stream, a);                                       \
     return hipGetLastError();                                                               \
+  }                                                                                         \
+  int NAME##_occupancy(int lds_bytes) { /* workgroups one CU holds at this LDS request */   \
+    int per = 0;                                                                            \
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, solve_kernel<MODE, MINW>, 64 * mode_waves(MODE), \
+                                                     (size_t)lds_bytes) != hipSuccess)      \
+      return -1;                                                                            \
+    return per;                                                                             \
   }                                                                                         \
   hipError_t NAME##_configure(int max_lds_bytes) {                                          \
     return hipFuncSetAttribute(reinterpret_cast<const void*>(&solve_kernel<MODE, MINW>),          \

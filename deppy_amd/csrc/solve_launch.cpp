@@ -18,23 +18,34 @@ hipError_t launch_split_configure(int);
 hipError_t launch_split4_configure(int);
 hipError_t launch_hbm_configure(int);
 hipError_t launch_ldsg_configure(int);
+int launch_lds_occupancy(int);
+int launch_lds_dense_occupancy(int);
 
-// The unbounded one-wavefront build runs 4 waves per SIMD (105 VGPRs, 16 per
-// CU).  A launch whose footprint lets LDS hold more problems than that per
-// CU takes the register-capped build (5 per SIMD, 20 per CU; 94 VGPRs);
-// larger footprints are LDS-bound (solve_kernel.hpp DP_LDS_MIN_WAVES).
+// The unbounded one-wavefront build runs 4 waves per SIMD (108 VGPRs, 16 per
+// CU).  A launch whose whole working set lets LDS hold more problems than
+// that per CU takes the register-capped build (5 per SIMD, 20 per CU; 94
+// VGPRs); larger footprints are LDS-bound (solve_kernel.hpp
+// DP_LDS_MIN_WAVES) and take the unbounded build, which keeps the CDCL-only
+// arrays in HBM scratch (layout.hpp mode_evict).  The rule looks at the
+// un-evicted footprint, so it picks the build for the launches it always did.
 constexpr int kUnboundedWavesPerCU = 16;
 constexpr int kLdsPerCU = 160 * 1024;
 
-hipError_t launch_solve(const KernelArgs& a, int mode, int n_blocks, int lds_bytes, hipStream_t stream) {
-  if (mode == M_LDS) {
-    static const bool no_dense = [] {  // diagnostic DEPPY_NO_DENSE=1: the unbounded build only
-      const char* e = std::getenv("DEPPY_NO_DENSE");
-      return e && *e && *e != '0';
-    }();
-    const bool dense = !no_dense && lds_bytes > 0 && kLdsPerCU / lds_bytes > kUnboundedWavesPerCU;
+bool lds_dense(int full_bytes) {
+  static const bool no_dense = [] {  // diagnostic DEPPY_NO_DENSE=1: the unbounded build only
+    const char* e = std::getenv("DEPPY_NO_DENSE");
+    return e && *e && *e != '0';
+  }();
+  return !no_dense && full_bytes > 0 && kLdsPerCU / full_bytes > kUnboundedWavesPerCU;
+}
+
+int lds_occupancy(int lds_bytes, bool dense) {
+  return dense ? launch_lds_dense_occupancy(lds_bytes) : launch_lds_occupancy(lds_bytes);
+}
+
+hipError_t launch_solve(const KernelArgs& a, int mode, int n_blocks, int lds_bytes, bool dense, hipStream_t stream) {
+  if (mode == M_LDS)
     return dense ? launch_lds_dense(a, n_blocks, lds_bytes, stream) : launch_lds(a, n_blocks, lds_bytes, stream);
-  }
   if (mode == M_SPLIT) return launch_split(a, n_blocks, lds_bytes, stream);
   if (mode == M_SPLIT4) return launch_split4(a, n_blocks, lds_bytes, stream);
   if (mode == M_LDSG) return launch_ldsg(a, n_blocks, lds_bytes, stream);

@@ -642,6 +642,20 @@ enum dp_place {
   DP_PLACE_TOO_LARGE = -2
 };
 int dp_plan_placements(const dp_batch* b, int32_t opt_flags, int8_t* place);
+/*   dp_plan_footprints: what the same plan requests for each problem on its
+ *     placement: lds_bytes[n_problems], the LDS footprint that buckets it and
+ *     that its launch requests the maximum of, and scratch_bytes[n_problems],
+ *     its HBM scratch (DP_PLACE_LDS: the state only Solve()'s conflict
+ *     analysis touches, kept out of the LDS image, unless its launch takes
+ *     the register-capped build, which keeps everything in LDS;
+ *     DP_PLACE_LDSG: 0).  0 / 0 for a problem that is not launched.
+ *     Returns 0 or -1.
+ *   dp_lds_occupancy: workgroups of the one-wavefront kernel (capped != 0: its
+ *     register-capped build) that one CU of the current device holds at an LDS
+ *     request of lds_bytes, as the HIP runtime reports it
+ *     (hipOccupancyMaxActiveBlocksPerMultiprocessor); -1 on error.  Needs a GPU. */
+int dp_plan_footprints(const dp_batch* b, int32_t opt_flags, int32_t* lds_bytes, int32_t* scratch_bytes);
+int dp_lds_occupancy(int32_t lds_bytes, int32_t capped);
 /*   dp_plan_order: the launch order dp_submit plans for b as one chunk:
  *     order[] (the problems, skipped ones left out, in workgroup order:
  *     launch after launch) and launch_first[] (each launch's first index
