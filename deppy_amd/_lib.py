@@ -98,7 +98,7 @@ EXPORTS = [
     "dp_stitch_selftest", "dp_partition", "dp_build_info", "dp_get_device_stats", "dp_plan_placements",
     "dp_plan_footprints", "dp_lds_occupancy",
     "dp_plan_order", "dp_dlower_new", "dp_dlower_free", "dp_lower_device", "dp_dlower_host_count",
-    "dp_host_alloc", "dp_host_free",
+    "dp_host_alloc", "dp_host_free", "dp_lower_solve", "dp_dlower_error", "dp_plan_order_heads",
 ]
 
 
@@ -136,6 +136,15 @@ class Wire32(ctypes.Structure):
         ("str_off", c_i64p),
         ("str_bytes", ctypes.c_char_p),
     ]
+
+
+class Solved(ctypes.Structure):
+    """dp_solved (include/deppy_hip.h): the results of dp_lower_solve, arrays
+    owned by the dp_dlower and valid until its next call."""
+    _fields_ = [("n_problems", ctypes.c_int32), ("err", c_i32p), ("status", c_i8p), ("flags", c_i32p),
+                ("steps", c_i64p), ("installed", c_u32p), ("inst_off", c_i64p), ("core_len", c_i32p),
+                ("core_off", c_i64p), ("core", c_i32p), ("core_var", c_i32p), ("core_con", c_i32p),
+                ("h2d_bytes", ctypes.c_int64), ("d2h_bytes", ctypes.c_int64), ("host_lowered", ctypes.c_int64)]
 
 
 class Opts(ctypes.Structure):
@@ -279,6 +288,9 @@ def lib():
     L.dp_lower_device.argtypes = [vp, ctypes.POINTER(Wire32), ctypes.c_int32, vp]
     L.dp_dlower_host_count.argtypes = [vp]
     L.dp_dlower_host_count.restype = ctypes.c_int64
+    L.dp_lower_solve.argtypes = [vp, ctypes.POINTER(Wire32), ctypes.POINTER(Solved)]
+    L.dp_dlower_error.argtypes = [vp, ctypes.c_int32, ctypes.POINTER(ctypes.c_char_p)]
+    L.dp_plan_order_heads.argtypes = [c_i32p, c_i64p, ctypes.c_int32, ctypes.c_int32, c_i32p, c_i32p]
     L.dp_host_alloc.argtypes = [ctypes.c_int64]
     L.dp_host_alloc.restype = vp
     L.dp_host_free.argtypes = [vp]
@@ -604,6 +616,37 @@ class DeviceLowerer:
         lw._fetch()
         return lw
 
+    def lower_solve(self, w32: Wire32Arrays) -> dict:
+        """dp_lower_solve: the compact wire lowered and solved with the
+        records left on the device.  -> views of the dp_solved arrays (valid
+        until this object's next call) plus msg (the error text of every
+        problem with err != 0), h2d_bytes, d2h_bytes and host_lowered."""
+        L = lib()
+        ws = w32.struct()
+        so = Solved()
+        if L.dp_lower_solve(self.h, ctypes.byref(ws), ctypes.byref(so)) != 0:
+            raise ValueError(L.dp_last_global_error().decode())
+        n = so.n_problems
+        out = dict(err=_view(self, so.err, n, ctypes.c_int32, np.int32),
+                   status=_view(self, so.status, n, ctypes.c_int8, np.int8),
+                   flags=_view(self, so.flags, n, ctypes.c_int32, np.int32),
+                   steps=_view(self, so.steps, n, ctypes.c_int64, np.int64),
+                   core_len=_view(self, so.core_len, n, ctypes.c_int32, np.int32),
+                   inst_off=_view(self, so.inst_off, n + 1, ctypes.c_int64, np.int64),
+                   core_off=_view(self, so.core_off, n + 1, ctypes.c_int64, np.int64))
+        ni, nc = int(out["inst_off"][-1]), int(out["core_off"][-1])
+        out["installed"] = _view(self, so.installed, ni, ctypes.c_uint32, np.uint32)
+        for k in ("core", "core_var", "core_con"):
+            out[k] = _view(self, getattr(so, k), nc, ctypes.c_int32, np.int32)
+        msg = [None] * n
+        m = ctypes.c_char_p()
+        for p in np.nonzero(out["err"])[0]:
+            L.dp_dlower_error(self.h, int(p), ctypes.byref(m))
+            msg[p] = m.value.decode("utf-8", "surrogateescape")
+        out.update(msg=msg, h2d_bytes=int(so.h2d_bytes), d2h_bytes=int(so.d2h_bytes),
+                   host_lowered=int(so.host_lowered))
+        return out
+
     @property
     def host_count(self) -> int:
         """Problems of the last call lowered on the host."""
@@ -885,6 +928,21 @@ def plan_order(rec_off, rec, flags: int = 0):
     nl = lib().dp_plan_order(ctypes.byref(_batch(rec_off, rec)), flags, _p(order, c_i32p), _p(first, c_i32p))
     if nl < 0:
         raise RuntimeError("dp_plan_order failed")
+    return order, first[:nl]
+
+
+def plan_order_heads(heads, rec_off, flags: int = 0):
+    """plan_order from the records' headers alone (dp_plan_order_heads):
+    heads[n, 16] and the records' offsets."""
+    rec_off = np.ascontiguousarray(rec_off, np.int64)
+    n = len(rec_off) - 1
+    heads = np.ascontiguousarray(heads if n else np.zeros((1, 16), np.int32), np.int32)
+    order = np.zeros(max(n, 1), np.int32)
+    first = np.zeros(32, np.int32)
+    nl = lib().dp_plan_order_heads(_p(heads, c_i32p), _p(rec_off, c_i64p), n, flags, _p(order, c_i32p),
+                                   _p(first, c_i32p))
+    if nl < 0:
+        raise RuntimeError("dp_plan_order_heads failed")
     return order, first[:nl]
 
 

@@ -18,5 +18,30 @@ LoweredOut lowered_prepare(dp_lowered* lw, int32_t P, int64_t rec_words, int64_t
 int lowered_splice(dp_lowered* lw, const dp_wire* sub, int32_t flags, const int32_t* which, int32_t nw);
 // The HIP ordinal of the context's first device (runtime.cpp).
 int ctx_first_ordinal(const dp_ctx* ctx);
+// The context's dp_opt_flag bits.
+int32_t ctx_flags(const dp_ctx* ctx);
+
+// A fused job's records (dp_lower_solve): left in device memory by the
+// lowering, with only their headers on the host.  Problem i's record is at
+// dev_rec + rec_off[i], its header at heads + i * DP_H_SIZE (all zero: no
+// record, the problem is not launched), its identity owners at dev_ivs /
+// dev_ics + i * owner_stride (dev_nid[i] of them).
+struct FusedSrc {
+  const int32_t* heads;    // host
+  const int64_t* rec_off;  // host [n+1]
+  const int32_t* dev_rec;  // device (of the context's first device)
+  const int32_t *dev_nid, *dev_ivs, *dev_ics;
+  int32_t owner_stride;
+  int32_t *core_var, *core_con;  // host: owners of res->core, indexed as it is
+};
+// dp_submit with byte accounting: *h2d / *d2h (may be null) grow by every
+// byte the job's chunks move over PCIe (kernel writes to and reads from
+// mapped host memory included) before dp_job_wait returns.  With `fused`,
+// the job is one chunk on the context's first device whose solve reads the
+// records where they lie; only its tables go to the device, and the owners
+// of the reported cores come back beside them.
+int submit_job(dp_ctx* ctx, const dp_batch* b, dp_result* res, const FusedSrc* fused, int64_t* h2d, int64_t* d2h,
+               dp_job** out);
+
 
 }  // namespace dp

@@ -96,6 +96,14 @@ int lds_occupancy(int lds_bytes, bool dense);
 // items: the watch lists of its DP_FMT_I32 records above DEV_WATCH_VARS
 // variables into their scratch (watch_build.hip).  Other items are skipped.
 hipError_t launch_watch_build(const KernelArgs& a, int mode, int n_items, hipStream_t stream);
+// After a fused chunk's solve launches, on their stream (core_owners.hip):
+// for each of the n_items work items whose problem reports a core, the owner
+// of every identity of the core -- own_var / own_con[core_at + k] = ivs / ics
+// [pid * stride + core[core_at + k]] -- beside the core pool (core_cap
+// words).  An identity outside [0, nid[pid]) gives -1.
+hipError_t launch_core_owners(const WorkItem* items, int n_items, const ProblemOut* out, const int32_t* core,
+                              int64_t core_cap, int32_t* own_var, int32_t* own_con, const int32_t* nid,
+                              const int32_t* ivs, const int32_t* ics, int32_t stride, hipStream_t stream);
 // Raise the kernel's dynamic-LDS limit to the device maximum.
 hipError_t configure_solve_kernel(int max_lds_bytes);
 

@@ -23,6 +23,15 @@
 // them in.  Then a scan gives the record and identity offsets, and a copy
 // kernel packs the slots into the batch, which goes back to page-locked host
 // memory.
+//
+// dp_lower_solve (the fused path) runs the same lowering kernel but neither
+// the scan nor the packing, and copies no record or owner back: each record
+// stays in its slot, where a solve job of the context's pipeline reads it
+// (runtime.cpp start_fused_chunk), and only its header and counts go to the
+// host (heads_kernel), which plans the launches from them.  The owners of
+// the reported cores are looked up on the device (core_owners.hip).  The
+// fused windows run on the device lowering's own device, the context's
+// first: sharding one wire over several devices is out of scope.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -726,6 +735,25 @@ __global__ void __launch_bounds__(DL_T) pack_kernel(int32_t p0, const int32_t* w
   }
 }
 
+// The fused path (dp_lower_solve) packs nothing: the solve reads each record
+// from its slot.  What the host needs to plan the launches goes to mapped
+// page-locked memory: the 16 header words of local problems [0, n) (zeros
+// for a problem left to the host) and their words / nid counts -- 72 bytes a
+// problem, the only part of the lowering's output that crosses PCIe.
+// Sixteen lanes per problem.
+constexpr int HEADS_T = 256;
+__global__ void __launch_bounds__(HEADS_T) heads_kernel(int32_t n, const int32_t* __restrict__ words,
+                                                        const int32_t* __restrict__ nid,
+                                                        const int32_t* __restrict__ slots, int32_t* __restrict__ heads,
+                                                        int32_t* __restrict__ counts) {
+  const int t = (int)blockIdx.x * HEADS_T + (int)threadIdx.x;
+  const int p = t / DP_H_SIZE, j = t % DP_H_SIZE;
+  if (p >= n) return;
+  const int32_t w = words[p];
+  heads[(int64_t)p * DP_H_SIZE + j] = w > 0 ? slots[(int64_t)p * DL_SLOT + j] : 0;
+  if (j < 2) counts[2 * (int64_t)p + j] = j ? (w > 0 ? nid[p] : 0) : w;
+}
+
 template <class T>
 struct DevBuf {
   T* p = nullptr;
@@ -745,10 +773,120 @@ struct DevBuf {
   }
 };
 
+// Page-locked host memory, grown on demand; new storage is zeroed.
+template <class T>
+struct PinBuf {
+  T* p = nullptr;
+  size_t cap = 0;
+  bool need(size_t n) {
+    if (n <= cap && p) return true;
+    if (p) dp::pinned_free(p);
+    p = nullptr;
+    cap = 0;
+    const size_t c = std::max<size_t>(n + n / 8, 64);
+    p = static_cast<T*>(dp::pinned_alloc(c * sizeof(T)));
+    if (!p) return false;
+    std::memset(p, 0, c * sizeof(T));
+    cap = c;
+    return true;
+  }
+  ~PinBuf() {
+    if (p) dp::pinned_free(p);
+  }
+};
+
+// Mapped page-locked memory a kernel writes (the headers): host and device address.
+struct MapBuf {
+  int32_t *h = nullptr, *d = nullptr;
+  size_t cap = 0;
+  hipError_t need(size_t n) {
+    if (n <= cap) return hipSuccess;
+    if (h) (void)hipHostFree(h);
+    h = d = nullptr;
+    cap = 0;
+    const size_t c = std::max<size_t>(n + n / 8, 256);
+    hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&h), c * sizeof(int32_t),
+                                 hipHostMallocPortable | hipHostMallocMapped);
+    if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void**>(&d), h, 0);
+    if (e != hipSuccess) {
+      if (h) (void)hipHostFree(h);
+      h = d = nullptr;
+      return e;
+    }
+    cap = c;
+    return hipSuccess;
+  }
+  ~MapBuf() {
+    if (h) (void)hipHostFree(h);
+  }
+};
+
+// One window of the fused path: the window's wire ranges, its slots and
+// owners on the device, its headers on the host, and the job solving it.
+struct FusedWin {
+  DevBuf<int32_t> pvo, pco, pao, vid, ckn, arg, words, nid, slots, ivs, ics;
+  DevBuf<uint16_t> vnc, cna, vid16, arg16;
+  MapBuf heads, counts;
+  hipEvent_t lowered = nullptr;
+  dp_job* job = nullptr;
+  int64_t job_h2d = 0, job_d2h = 0;  // the job's PCIe bytes (its own counters: jobs run side by side)
+  int32_t q0 = 0, n = 0;
+  ~FusedWin() {
+    if (lowered) (void)hipEventDestroy(lowered);
+  }
+};
+
+// Core identities and their owners of one result layout.  The kernels and the
+// scatter write only the reported cores; the ranges a call wrote are zeroed
+// at the start of the next, so the rest of the arrays stays zero (as a
+// caller's fresh dp_result is) without a pass over all of it per call.
+struct CoreSet {
+  PinBuf<int32_t> core, cvar, ccon;
+  std::vector<std::pair<int64_t, int32_t>> dirty;
+  bool need(size_t n) {
+    if (n > core.cap || n > cvar.cap || n > ccon.cap) dirty.clear();  // (new storage is zeroed)
+    return core.need(n) && cvar.need(n) && ccon.need(n);
+  }
+  void clean() {
+    for (const auto& r : dirty) {
+      std::memset(core.p + r.first, 0, (size_t)r.second * 4);
+      std::memset(cvar.p + r.first, 0, (size_t)r.second * 4);
+      std::memset(ccon.p + r.first, 0, (size_t)r.second * 4);
+    }
+    dirty.clear();
+  }
+  void wipe() {  // (after a failed call: what it wrote is not recorded)
+    if (core.p) std::memset(core.p, 0, core.cap * 4);
+    if (cvar.p) std::memset(cvar.p, 0, cvar.cap * 4);
+    if (ccon.p) std::memset(ccon.p, 0, ccon.cap * 4);
+    dirty.clear();
+  }
+};
+
+constexpr int32_t kFusedWindow = 16384;  // problems per window: 320 MiB of slots and owners at most
+
 }  // namespace
 
 struct dp_dlower {
   int dev = 0;
+  dp_ctx* ctx = nullptr;  // dp_lower_solve submits its jobs to it
+  // -- dp_lower_solve --
+  FusedWin fw[2];
+  std::vector<int64_t> f_rec_off;  // [window + 1]: slot i at i * DL_SLOT
+  PinBuf<int32_t> o_err, o_flags, o_core_len;
+  PinBuf<int8_t> o_status;
+  PinBuf<int64_t> o_steps;
+  // the fused windows' layout (a problem left to the host takes no room),
+  // the host-lowered problems' own, and the two merged by problem index
+  PinBuf<int64_t> v_inst_off, v_core_off, s_inst_off, s_core_off, m_inst_off, m_core_off;
+  PinBuf<uint32_t> v_inst, s_inst, m_inst;
+  CoreSet v_core, s_core, m_core;
+  PinBuf<int32_t> s_flags, s_core_len;
+  PinBuf<int8_t> s_status;
+  PinBuf<int64_t> s_steps;
+  dp_lowered* side = nullptr;   // the host-lowered problems' records
+  std::vector<int32_t> f_which;  // the problems of the last dp_lower_solve lowered on the host (ascending)
+  std::vector<int32_t> f_err;    // their enum dp_lower_err
   hipStream_t st = nullptr;   // kernels and the copies back
   hipStream_t cst = nullptr;  // the wire's copies to the device
   hipStream_t pst = nullptr;  // the packing (its writes to host memory run under the next piece's lowering)
@@ -768,6 +906,7 @@ struct dp_dlower {
   std::vector<int64_t> s_sz, s_off;
   std::mutex mu;  // one call at a time
   ~dp_dlower() {
+    if (side) dp_lowered_free(side);
     if (h_off) dp::pinned_free(h_off);
     for (auto e : ev)
       if (e) (void)hipEventDestroy(e);
@@ -906,6 +1045,21 @@ bool dl_times() {
   return on;
 }
 
+// Problems past the kernel's sizes are lowered on the host: when they hold
+// most of the batch's arguments, the whole batch is (a device pass and a
+// splice would only add to the host's work).
+bool device_takes(const dp_wire32* w) {
+  const int32_t P = w->n_problems;
+  int64_t fit_args = 0, all_args = (int64_t)w->prob_arg_off[P] - w->prob_arg_off[0];
+  for (int32_t p = 0; p < P; ++p) {
+    const int32_t nv = w->prob_var_off[p + 1] - w->prob_var_off[p];
+    const int32_t nc = w->prob_con_off[p + 1] - w->prob_con_off[p];
+    const int32_t na = w->prob_arg_off[p + 1] - w->prob_arg_off[p];
+    if (nv >= 1 && nv <= DL_NV && nc <= DL_C && na <= DL_A) fit_args += na + 1;
+  }
+  return 2 * fit_args >= all_args + P;
+}
+
 bool monotone(const int32_t* o, int32_t P) {
   if (!o || o[0] < 0) return false;
   for (int32_t p = 0; p < P; ++p)
@@ -935,11 +1089,13 @@ dp_dlower* dp_dlower_new(dp_ctx* ctx) {
   }
   auto* d = new dp_dlower;
   d->dev = dev;
+  d->ctx = ctx;
   bool ok = hipSetDevice(dev) == hipSuccess && hipStreamCreateWithFlags(&d->st, hipStreamNonBlocking) == hipSuccess &&
             hipStreamCreateWithFlags(&d->cst, hipStreamNonBlocking) == hipSuccess &&
             dl_pack_stream(&d->pst) == hipSuccess;
   for (auto& e : d->ev) ok = ok && hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
   for (auto& e : d->es) ok = ok && hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
+  for (auto& f : d->fw) ok = ok && hipEventCreateWithFlags(&f.lowered, hipEventDisableTiming) == hipSuccess;
   if (!ok) {
     dp::set_global_error("dp_dlower_new: stream creation failed");
     delete d;
@@ -963,19 +1119,7 @@ int dp_lower_device(dp_dlower* d, const dp_wire32* w, int32_t flags, dp_lowered*
   const bool ours = (flags & (DP_LOWER_NARROW | DP_LOWER_PACKED)) == (DP_LOWER_NARROW | DP_LOWER_PACKED) &&
                     !(flags & DP_LOWER_NO_P8) && dp::ldsg_env() != dp::LDSG_ALWAYS && P > 0;
   if (!ours) return lower_on_host(w, flags, lw, d);
-  // problems past the kernel's sizes are lowered on the host: when they
-  // hold most of the batch's arguments, the whole batch is (a device pass and
-  // a splice would only add to the host's work)
-  {
-    int64_t fit_args = 0, all_args = (int64_t)w->prob_arg_off[P] - w->prob_arg_off[0];
-    for (int32_t p = 0; p < P; ++p) {
-      const int32_t nv = w->prob_var_off[p + 1] - w->prob_var_off[p];
-      const int32_t nc = w->prob_con_off[p + 1] - w->prob_con_off[p];
-      const int32_t na = w->prob_arg_off[p + 1] - w->prob_arg_off[p];
-      if (nv >= 1 && nv <= DL_NV && nc <= DL_C && na <= DL_A) fit_args += na + 1;
-    }
-    if (2 * fit_args < all_args + P) return lower_on_host(w, flags, lw, d);
-  }
+  if (!device_takes(w)) return lower_on_host(w, flags, lw, d);
   const int32_t pv0 = w->prob_var_off[0], cb0 = w->prob_con_off[0], ab0 = w->prob_arg_off[0];
   const int32_t nvars = w->prob_var_off[P] - pv0, ncons = w->prob_con_off[P] - cb0, nargs = w->prob_arg_off[P] - ab0;
   const bool ids16 = w->var_id16 != nullptr;
@@ -1155,6 +1299,451 @@ int dp_lower_device(dp_dlower* d, const dp_wire32* w, int32_t flags, dp_lowered*
     std::fprintf(stderr, "dp_lower_device: P %d device %.3f pack %.3f sub-wire %.3f splice %.3f ms (%d on the host)\n", P,
                  t_dev - t0, t_pack - t0, t_sub - t_pack, dl_ms() - t_sub, (int)d->which.size());
   return 0;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// dp_lower_solve: lowering and solve fused, records and owners stay in HBM
+// ---------------------------------------------------------------------------
+namespace {
+
+struct FusedTimes {
+  double lower_wait = 0, plan = 0, host = 0, wait = 0, merge = 0;
+};
+
+// Enqueue the wire copy, the lowering and the header kernel of window
+// [q0, q1) into B (the window as a batch of its own: offsets from its first
+// element), recording B.lowered behind them.  Returns the bytes copied to the
+// device, or -1.
+int64_t enqueue_window(dp_dlower* d, FusedWin& B, const dp_wire32* w, int32_t q0, int32_t q1) {
+  const int32_t n = q1 - q0;
+  const int32_t pv0 = w->prob_var_off[q0], cb0 = w->prob_con_off[q0], ab0 = w->prob_arg_off[q0];
+  const int32_t nvars = w->prob_var_off[q1] - pv0, ncons = w->prob_con_off[q1] - cb0,
+                nargs = w->prob_arg_off[q1] - ab0;
+  const bool ids16 = w->var_id16 != nullptr;
+  B.q0 = q0;
+  B.n = n;
+  DL_OK(B.pvo.need((size_t)n + 1));
+  DL_OK(B.pco.need((size_t)n + 1));
+  DL_OK(B.pao.need((size_t)n + 1));
+  if (ids16) {
+    DL_OK(B.vid16.need((size_t)nvars + 1));
+    DL_OK(B.arg16.need((size_t)nargs + 1));
+  } else {
+    DL_OK(B.vid.need((size_t)nvars + 1));
+    DL_OK(B.arg.need((size_t)nargs + 1));
+  }
+  DL_OK(B.vnc.need((size_t)nvars + 1));
+  DL_OK(B.ckn.need((size_t)ncons + 1));
+  DL_OK(B.cna.need((size_t)ncons + 1));
+  DL_OK(B.words.need((size_t)n));
+  DL_OK(B.nid.need((size_t)n));
+  DL_OK(B.slots.need((size_t)n * DL_SLOT));
+  DL_OK(B.ivs.need((size_t)n * DL_C));
+  DL_OK(B.ics.need((size_t)n * DL_C));
+  DL_OK(B.heads.need((size_t)n * DP_H_SIZE));
+  DL_OK(B.counts.need((size_t)n * 2));
+  hipStream_t st = d->st, cst = d->cst;
+  int64_t bytes = 0;
+  auto h2d = [&](auto* dst, const auto* src, int64_t m) {
+    bytes += m > 0 ? m * (int64_t)sizeof(*src) : 0;
+    return m > 0 ? hipMemcpyAsync(dst, src, (size_t)m * sizeof(*src), hipMemcpyHostToDevice, cst) : hipSuccess;
+  };
+  DL_OK(h2d(B.pvo.p, w->prob_var_off + q0, (int64_t)n + 1));
+  DL_OK(h2d(B.pco.p, w->prob_con_off + q0, (int64_t)n + 1));
+  DL_OK(h2d(B.pao.p, w->prob_arg_off + q0, (int64_t)n + 1));
+  DlArgs a{};
+  a.pvo = B.pvo.p;
+  a.pco = B.pco.p;
+  a.pao = B.pao.p;
+  a.vid = B.vid.p;
+  a.vnc = B.vnc.p;
+  a.ckn = B.ckn.p;
+  a.cna = B.cna.p;
+  a.arg = B.arg.p;
+  a.vid16 = B.vid16.p;
+  a.arg16 = B.arg16.p;
+  a.ids16 = ids16 ? 1 : 0;
+  a.pbase = pv0;
+  a.cbase = cb0;
+  a.abase = ab0;
+  a.nvars = nvars;
+  a.ncons = ncons;
+  a.nargs = nargs;
+  a.n_strs = w->n_strs;
+  a.group_above = dp::group_above();
+  a.words = B.words.p;
+  a.nid = B.nid.p;
+  a.slots = B.slots.p;
+  a.ivs = B.ivs.p;
+  a.ics = B.ics.p;
+  // pieces, as dp_lower_device: piece k+1's copy runs under piece k's lowering
+  const int pieces = (int)std::min<int64_t>(dp_dlower::kMaxPieces, std::max<int64_t>(1, n / 2048));
+  auto piece = [&](int k) { return q0 + (int32_t)((int64_t)n * k / pieces); };
+  for (int k = 0; k < pieces; ++k) {
+    const int32_t r0 = piece(k), r1 = piece(k + 1);
+    const int32_t v0 = w->prob_var_off[r0], v1 = w->prob_var_off[r1];
+    const int32_t c0 = w->prob_con_off[r0], c1 = w->prob_con_off[r1];
+    const int32_t x0 = w->prob_arg_off[r0], x1 = w->prob_arg_off[r1];
+    if (ids16) DL_OK(h2d(B.vid16.p + (v0 - pv0), w->var_id16 + v0, v1 - v0));
+    else DL_OK(h2d(B.vid.p + (v0 - pv0), w->var_id + v0, v1 - v0));
+    DL_OK(h2d(B.vnc.p + (v0 - pv0), w->var_ncon + v0, v1 - v0));
+    DL_OK(h2d(B.ckn.p + (c0 - cb0), w->con_kn + c0, c1 - c0));
+    DL_OK(h2d(B.cna.p + (c0 - cb0), w->con_nargs + c0, c1 - c0));
+    if (ids16) DL_OK(h2d(B.arg16.p + (x0 - ab0), w->con_arg16 + x0, x1 - x0));
+    else DL_OK(h2d(B.arg.p + (x0 - ab0), w->con_arg + x0, x1 - x0));
+    DL_OK(hipEventRecord(d->ev[k], cst));
+  }
+  for (int k = 0; k < pieces; ++k) {
+    const int32_t r0 = piece(k), r1 = piece(k + 1);
+    DL_OK(hipStreamWaitEvent(st, d->ev[k], 0));
+    if (r1 == r0) continue;
+    a.p0 = r0 - q0;
+    hipLaunchKernelGGL(lower_kernel, dim3((unsigned)(r1 - r0)), dim3(DL_T), 0, st, a);
+    DL_OK(hipGetLastError());
+  }
+  hipLaunchKernelGGL(heads_kernel, dim3((unsigned)(((int64_t)n * DP_H_SIZE + HEADS_T - 1) / HEADS_T)), dim3(HEADS_T),
+                     0, st, n, B.words.p, B.nid.p, B.slots.p, B.heads.d, B.counts.d);
+  DL_OK(hipGetLastError());
+  DL_OK(hipEventRecord(B.lowered, st));
+  return bytes;
+}
+
+int32_t fused_window() {  // (read per call)
+  const char* e = std::getenv("DEPPY_FUSED_WINDOW");
+  const long long v = e && *e ? std::atoll(e) : 0;
+  return v > 0 ? (int32_t)std::min<long long>(v, kFusedWindow) : kFusedWindow;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dp_lower_solve(dp_dlower* d, const dp_wire32* w, dp_solved* out) {
+  if (!d || !w || !out) {
+    dp::set_global_error("dp_lower_solve: null argument");
+    return -1;
+  }
+  if (w->n_problems < 0 || !monotone(w->prob_var_off, w->n_problems) || !monotone(w->prob_con_off, w->n_problems) ||
+      !monotone(w->prob_arg_off, w->n_problems)) {
+    dp::set_global_error("dp_lower: malformed wire batch");
+    return -1;
+  }
+  std::lock_guard<std::mutex> lk(d->mu);
+  const double t0 = dl_ms();
+  FusedTimes tm;
+  const int32_t P = w->n_problems;
+  *out = dp_solved{};
+  d->f_which.clear();
+  d->f_err.clear();
+  d->host_count = 0;
+  d->v_core.clean();
+  d->s_core.clean();
+  d->m_core.clean();
+  if (!d->o_err.need((size_t)P + 1) || !d->o_flags.need((size_t)P + 1) || !d->o_core_len.need((size_t)P + 1) ||
+      !d->o_status.need((size_t)P + 1) || !d->o_steps.need((size_t)P + 1) || !d->v_inst_off.need((size_t)P + 1) ||
+      !d->v_core_off.need((size_t)P + 1)) {
+    dp::set_global_error("dp_lower_solve: page-locked allocation failed");
+    return -1;
+  }
+  std::memset(d->o_err.p, 0, ((size_t)P + 1) * sizeof(int32_t));
+  d->v_inst_off.p[0] = d->v_core_off.p[0] = 0;
+  out->n_problems = P;
+  out->err = d->o_err.p;
+  out->status = d->o_status.p;
+  out->flags = d->o_flags.p;
+  out->steps = d->o_steps.p;
+  out->core_len = d->o_core_len.p;
+  out->inst_off = d->v_inst_off.p;
+  out->core_off = d->v_core_off.p;
+  if (P == 0) {
+    if (!d->v_inst.need(1) || !d->v_core.need(1)) {
+      dp::set_global_error("dp_lower_solve: page-locked allocation failed");
+      return -1;
+    }
+    out->installed = d->v_inst.p;
+    out->core = d->v_core.core.p;
+    out->core_var = d->v_core.cvar.p;
+    out->core_con = d->v_core.ccon.p;
+    return 0;
+  }
+  const int32_t pv0 = w->prob_var_off[0], cb0 = w->prob_con_off[0], ab0 = w->prob_arg_off[0];
+  const int32_t nvars = w->prob_var_off[P] - pv0, ncons = w->prob_con_off[P] - cb0, nargs = w->prob_arg_off[P] - ab0;
+  const bool ids16 = w->var_id16 != nullptr;
+  if ((nvars > 0 && (!(ids16 ? (const void*)w->var_id16 : (const void*)w->var_id) || !w->var_ncon)) ||
+      (ncons > 0 && (!w->con_kn || !w->con_nargs)) ||
+      (nargs > 0 && !(ids16 ? (const void*)w->con_arg16 : (const void*)w->con_arg)) ||
+      (ids16 && w->n_strs > 65536)) {
+    dp::set_global_error("dp_lower: malformed wire batch");
+    return -1;
+  }
+  // The device path, unless the records would not be the forms the solve
+  // reads as they lie: placement overrides stage other forms on the host.
+  const int32_t forced = DP_OPT_FORCE_GROUP | DP_OPT_FORCE_HBM | DP_OPT_FORCE_MID | DP_OPT_FORCE_LDSG;
+  const bool on_device = !(dp::ctx_flags(d->ctx) & forced) && dp::ldsg_env() != dp::LDSG_ALWAYS && device_takes(w);
+  std::vector<int32_t>& which = d->which;
+  which.clear();
+  int64_t h2d = 0, d2h = 0;  // this thread's copies, then each waited job's
+  int64_t sh2d = 0, sd2h = 0;  // the host-lowered problems' job
+  bool enqueued = false;
+  // Every job still in flight is waited for, and (after the first enqueue)
+  // the lowering's streams are synchronised, before an error returns.
+  auto settle = [&]() {
+    int rc = 0;
+    for (auto& B : d->fw)
+      if (B.job) {
+        if (dp_job_wait(d->ctx, B.job)) rc = -1;
+        B.job = nullptr;
+        h2d += B.job_h2d;
+        d2h += B.job_d2h;
+      }
+    return rc;
+  };
+  auto fail = [&](const char* text) {
+    const std::string keep = text ? std::string(text) : std::string(dp_last_global_error());
+    if (enqueued) {
+      (void)hipStreamSynchronize(d->cst);
+      (void)hipStreamSynchronize(d->st);
+    }
+    (void)settle();
+    d->v_core.wipe();
+    d->s_core.wipe();
+    d->m_core.wipe();
+    dp::set_global_error(keep);
+    return -1;
+  };
+  if (on_device) {
+    if (hipSetDevice(d->dev) != hipSuccess) return fail("dp_lower_solve: hipSetDevice failed");
+    // Windows: at most `win` problems' slots and owners live at once.  A
+    // batch of several windows alternates two buffers of half a window each,
+    // so window k+1 is copied and lowered under window k's solve.
+    const int32_t W = fused_window();
+    const int32_t win = P <= W ? P : std::max<int32_t>(1, W / 2);
+    const int32_t nwin = (P + win - 1) / win;
+    // staging of the fused windows' results, sized from the wire's totals (a
+    // bitmap word per 32 variables, an identity per constraint at most)
+    int64_t inst_cap = 0;
+    for (int32_t p = 0; p < P; ++p) inst_cap += dp::bits_words(w->prob_var_off[p + 1] - w->prob_var_off[p]);
+    if (!d->v_inst.need((size_t)inst_cap + 1) || !d->v_core.need((size_t)ncons + 1))
+      return fail("dp_lower_solve: page-locked allocation failed");
+    if (d->f_rec_off.size() < (size_t)win + 1) {
+      d->f_rec_off.resize((size_t)win + 1);
+      for (int32_t i = 0; i <= win; ++i) d->f_rec_off[(size_t)i] = (int64_t)i * DL_SLOT;
+    }
+    auto range = [&](int k, int32_t& q0, int32_t& q1) {
+      q0 = k * win;
+      q1 = std::min<int64_t>(P, (int64_t)q0 + win);
+    };
+    int32_t q0, q1;
+    range(0, q0, q1);
+    enqueued = true;
+    int64_t b = enqueue_window(d, d->fw[0], w, q0, q1);
+    if (b < 0) return fail(nullptr);
+    h2d += b;
+    for (int k = 0; k < nwin; ++k) {
+      FusedWin& B = d->fw[k & 1];
+      const double ta = dl_ms();
+      if (hipEventSynchronize(B.lowered) != hipSuccess) return fail("dp_lower_solve: the lowering failed on the device");
+      const double tb = dl_ms();
+      tm.lower_wait += tb - ta;
+      d2h += (int64_t)B.n * (DP_H_SIZE + 2) * 4;
+      // the window's result layout from its headers; problems without a
+      // record go to the host
+      int64_t* io = d->v_inst_off.p + B.q0;
+      int64_t* co = d->v_core_off.p + B.q0;
+      for (int32_t i = 0; i < B.n; ++i) {
+        const int32_t words = B.counts.h[2 * (size_t)i];
+        const int32_t* h = B.heads.h + (size_t)i * DP_H_SIZE;
+        if (words <= 0) which.push_back(B.q0 + i);
+        io[i + 1] = io[i] + (words > 0 ? dp::bits_words(h[DP_H_NV]) : 0);
+        co[i + 1] = co[i] + (words > 0 ? std::max(0, B.counts.h[2 * (size_t)i + 1]) : 0);
+      }
+      if (io[B.n] > inst_cap || co[B.n] > (int64_t)ncons) return fail("dp_lower_solve: inconsistent record headers");
+      dp::FusedSrc F{};
+      F.heads = B.heads.h;
+      F.rec_off = d->f_rec_off.data();
+      F.dev_rec = B.slots.p;
+      F.dev_nid = B.nid.p;
+      F.dev_ivs = B.ivs.p;
+      F.dev_ics = B.ics.p;
+      F.owner_stride = DL_C;
+      F.core_var = d->v_core.cvar.p;
+      F.core_con = d->v_core.ccon.p;
+      dp_batch fb{B.n, d->f_rec_off.data(), nullptr};
+      dp_result fr{};
+      fr.status = d->o_status.p + B.q0;
+      fr.flags = d->o_flags.p + B.q0;
+      fr.steps = d->o_steps.p + B.q0;
+      fr.core_len = d->o_core_len.p + B.q0;
+      fr.installed = d->v_inst.p;
+      fr.inst_off = io;
+      fr.core = d->v_core.core.p;
+      fr.core_off = co;
+      B.job_h2d = B.job_d2h = 0;
+      if (dp::submit_job(d->ctx, &fb, &fr, &F, &B.job_h2d, &B.job_d2h, &B.job) != 0)
+        return fail("dp_lower_solve: the solve could not be submitted");
+      tm.plan += dl_ms() - tb;
+      if (k + 1 < nwin) {
+        FusedWin& N = d->fw[(k + 1) & 1];
+        if (N.job) {  // window k-1: its solve reads the slots window k+1 is lowered into
+          const double tw = dl_ms();
+          const int rc = dp_job_wait(d->ctx, N.job);
+          N.job = nullptr;
+          h2d += N.job_h2d;
+          d2h += N.job_d2h;
+          tm.wait += dl_ms() - tw;
+          if (rc) return fail(dp_last_error(d->ctx));
+        }
+        range(k + 1, q0, q1);
+        b = enqueue_window(d, N, w, q0, q1);
+        if (b < 0) return fail(nullptr);
+        h2d += b;
+      }
+    }
+  } else {
+    which.resize((size_t)P);
+    for (int32_t p = 0; p < P; ++p) which[(size_t)p] = p;
+  }
+  // The problems left to the host: lowered there while the fused windows
+  // solve, then solved as an ordinary job beside them.
+  const int32_t nw = (int32_t)which.size();
+  dp_job* sjob = nullptr;
+  const double th = dl_ms();
+  if (nw > 0) {
+    dp_wire sub{};
+    host_subwire(d, w, &sub);
+    if (!d->side) d->side = dp_lowered_new();
+    if (dp_lower_into(&sub, DP_LOWER_NARROW | DP_LOWER_PACKED | DP_LOWER_PINNED, d->side) != 0)
+      return fail("dp_lower: malformed wire batch");
+    dp_batch sb{nw, dp_lowered_rec_off(d->side), dp_lowered_rec(d->side)};
+    if (!d->s_inst_off.need((size_t)nw + 1) || !d->s_core_off.need((size_t)nw + 1) ||
+        dp_result_layout(&sb, d->s_inst_off.p, d->s_core_off.p) != 0 ||
+        !d->s_inst.need((size_t)d->s_inst_off.p[nw] + 1) || !d->s_core.need((size_t)d->s_core_off.p[nw] + 1) ||
+        !d->s_flags.need((size_t)nw) || !d->s_core_len.need((size_t)nw) || !d->s_status.need((size_t)nw) ||
+        !d->s_steps.need((size_t)nw))
+      return fail("dp_lower_solve: page-locked allocation failed");
+    d->f_err.assign((size_t)nw, 0);
+    (void)dp_lowered_errors(d->side, d->f_err.data());
+    dp_result sr{};
+    sr.status = d->s_status.p;
+    sr.flags = d->s_flags.p;
+    sr.steps = d->s_steps.p;
+    sr.core_len = d->s_core_len.p;
+    sr.installed = d->s_inst.p;
+    sr.inst_off = d->s_inst_off.p;
+    sr.core = d->s_core.core.p;
+    sr.core_off = d->s_core_off.p;
+    if (dp::submit_job(d->ctx, &sb, &sr, nullptr, &sh2d, &sd2h, &sjob) != 0)
+      return fail("dp_lower_solve: the solve could not be submitted");
+  }
+  const double tw = dl_ms();
+  tm.host = tw - th;
+  int rc = settle();
+  if (sjob && dp_job_wait(d->ctx, sjob)) rc = -1;
+  if (rc) return fail(dp_last_error(d->ctx));
+  const double tmg = dl_ms();
+  tm.wait += tmg - tw;
+  // the reported cores of the fused windows (their ranges are zeroed again by the next call)
+  if (on_device)
+    for (int32_t p = 0; p < P; ++p)
+      if (d->o_core_len.p[p] > 0 && d->v_core_off.p[p + 1] > d->v_core_off.p[p])
+        d->v_core.dirty.emplace_back(d->v_core_off.p[p], d->o_core_len.p[p]);
+  if (nw == 0) {
+    out->installed = d->v_inst.p;
+    out->core = d->v_core.core.p;
+    out->core_var = d->v_core.cvar.p;
+    out->core_con = d->v_core.ccon.p;
+  } else {
+    // the host-lowered problems' owners: identity -> AppliedConstraint on the host
+    const int64_t* io = dp_lowered_ident_off(d->side);
+    const int32_t* iv = dp_lowered_ident_var(d->side);
+    const int32_t* ic = dp_lowered_ident_con(d->side);
+    for (int32_t j = 0; j < nw; ++j) {
+      const int32_t len = d->s_core_len.p[j];
+      if (len <= 0) continue;
+      const int64_t at = d->s_core_off.p[j], nid = io[j + 1] - io[j];
+      for (int32_t k = 0; k < len; ++k) {
+        const int32_t id = d->s_core.core.p[at + k];
+        const bool ok = id >= 0 && id < nid;
+        d->s_core.cvar.p[at + k] = ok ? iv[io[j] + id] : -1;
+        d->s_core.ccon.p[at + k] = ok ? ic[io[j] + id] : -1;
+      }
+      d->s_core.dirty.emplace_back(at, len);
+    }
+    for (int32_t j = 0; j < nw; ++j) {
+      const int32_t p = which[(size_t)j];
+      d->o_err.p[p] = d->f_err[(size_t)j];
+      d->o_status.p[p] = d->s_status.p[j];
+      d->o_flags.p[p] = d->s_flags.p[j];
+      d->o_steps.p[p] = d->s_steps.p[j];
+      d->o_core_len.p[p] = d->s_core_len.p[j];
+    }
+    if (nw == P) {  // all on the host: its layout is the result's
+      out->inst_off = d->s_inst_off.p;
+      out->core_off = d->s_core_off.p;
+      out->installed = d->s_inst.p;
+      out->core = d->s_core.core.p;
+      out->core_var = d->s_core.cvar.p;
+      out->core_con = d->s_core.ccon.p;
+    } else {  // merged by problem index
+      if (!d->m_inst_off.need((size_t)P + 1) || !d->m_core_off.need((size_t)P + 1))
+        return fail("dp_lower_solve: page-locked allocation failed");
+      int64_t* mi = d->m_inst_off.p;
+      int64_t* mc = d->m_core_off.p;
+      mi[0] = mc[0] = 0;
+      for (int32_t p = 0, j = 0; p < P; ++p) {
+        const bool host = j < nw && which[(size_t)j] == p;
+        mi[p + 1] = mi[p] + (host ? d->s_inst_off.p[j + 1] - d->s_inst_off.p[j]
+                                  : d->v_inst_off.p[p + 1] - d->v_inst_off.p[p]);
+        mc[p + 1] = mc[p] + (host ? d->s_core_off.p[j + 1] - d->s_core_off.p[j]
+                                  : d->v_core_off.p[p + 1] - d->v_core_off.p[p]);
+        j += host;
+      }
+      if (!d->m_inst.need((size_t)mi[P] + 1) || !d->m_core.need((size_t)mc[P] + 1))
+        return fail("dp_lower_solve: page-locked allocation failed");
+      for (int32_t p = 0, j = 0; p < P; ++p) {
+        const bool host = j < nw && which[(size_t)j] == p;
+        const uint32_t* si = host ? d->s_inst.p + d->s_inst_off.p[j] : d->v_inst.p + d->v_inst_off.p[p];
+        std::memcpy(d->m_inst.p + mi[p], si, (size_t)(mi[p + 1] - mi[p]) * 4);
+        const int32_t len = (int32_t)std::min<int64_t>(d->o_core_len.p[p], mc[p + 1] - mc[p]);
+        if (len > 0) {
+          const CoreSet& S = host ? d->s_core : d->v_core;
+          const int64_t at = host ? d->s_core_off.p[j] : d->v_core_off.p[p];
+          std::memcpy(d->m_core.core.p + mc[p], S.core.p + at, (size_t)len * 4);
+          std::memcpy(d->m_core.cvar.p + mc[p], S.cvar.p + at, (size_t)len * 4);
+          std::memcpy(d->m_core.ccon.p + mc[p], S.ccon.p + at, (size_t)len * 4);
+          d->m_core.dirty.emplace_back(mc[p], len);
+        }
+        j += host;
+      }
+      out->inst_off = mi;
+      out->core_off = mc;
+      out->installed = d->m_inst.p;
+      out->core = d->m_core.core.p;
+      out->core_var = d->m_core.cvar.p;
+      out->core_con = d->m_core.ccon.p;
+    }
+  }
+  d->f_which = which;
+  d->host_count = nw;
+  out->h2d_bytes = h2d + sh2d;
+  out->d2h_bytes = d2h + sd2h;
+  out->host_lowered = nw;
+  if (dl_times())
+    std::fprintf(stderr,
+                 "dp_lower_solve: P %d total %.3f ms: lowering wait %.3f plan+submit %.3f host lowering %.3f "
+                 "solve wait %.3f merge %.3f (%d on the host)\n",
+                 P, dl_ms() - t0, tm.lower_wait, tm.plan, tm.host, tm.wait, dl_ms() - tmg, nw);
+  return 0;
+}
+
+int32_t dp_dlower_error(const dp_dlower* d, int32_t p, const char** msg) {
+  if (msg) *msg = "";
+  if (!d) return 0;
+  const auto it = std::lower_bound(d->f_which.begin(), d->f_which.end(), p);
+  if (it == d->f_which.end() || *it != p || !d->side) return 0;
+  return dp_lowered_error(d->side, (int32_t)(it - d->f_which.begin()), msg);
 }
 
 }  // extern "C"

@@ -304,13 +304,29 @@ void read_head(Head& H, const int32_t* h, int64_t avail, int32_t opt_flags, bool
     H.place = -2;
 }
 
-// rec + rec_off[p0 + i] is local problem i.  Problems whose header is not
+// Where plan_chunk finds a chunk's records: the plan reads nothing of a
+// record but its header and its extent.  Either the records themselves
+// (rec + rec_off[p]), or a dense array of their headers (heads + p *
+// DP_H_SIZE) with rec_off giving only the extents and alignment -- the
+// records may then lie where the host cannot read them (device memory).
+struct RecSrc {
+  const int32_t* rec;
+  const int64_t* rec_off;
+  const int32_t* heads = nullptr;
+  const int32_t* head(int64_t p) const { return heads ? heads + p * DP_H_SIZE : rec + rec_off[p]; }
+  int64_t extent(int64_t p) const { return rec_off[p + 1] - rec_off[p]; }
+  bool aligned(int64_t p) const { return (rec_off[p] & 3) == 0; }
+  // (a dense header array stands for records on a 16-byte boundary)
+  bool base_aligned() const { return heads ? true : ((uintptr_t)rec & 15) == 0; }
+};
+
+// R.head(p0 + i) is local problem i.  Problems whose header is not
 // well formed are planned as skipped (the caller reports them).  pool (may
 // be null) reads the headers in parallel.
 // ldsg_busy: M_LDSG problems already in flight on the device (the
 // pipeline's other lanes), counted against kLdsgMaxProblems with the chunk's.
-void plan_chunk(Plan& P, const int32_t* rec, const int64_t* rec_off, int32_t p0, int32_t n,
-                int32_t opt_flags, std::vector<uint8_t>* bad, Pool* pool = nullptr, int32_t ldsg_busy = 0) {
+void plan_chunk(Plan& P, const RecSrc& R, int32_t p0, int32_t n, int32_t opt_flags, std::vector<uint8_t>* bad,
+                Pool* pool = nullptr, int32_t ldsg_busy = 0) {
   P.n = n;
   P.n_ldsg = 0;
   P.img_off.resize((size_t)n + 1);
@@ -352,12 +368,11 @@ void plan_chunk(Plan& P, const int32_t* rec, const int64_t* rec_off, int32_t p0,
     for (int32_t i = i0; i < i1; ++i) {
       // every header is a cache miss: keep the next ones in flight
       if (i + 8 < i1) {
-        const int32_t* h8 = rec + rec_off[p0 + i + 8];
+        const int32_t* h8 = R.head(p0 + i + 8);
         __builtin_prefetch(h8);
         __builtin_prefetch(h8 + 15);
       }
-      read_head(head[i], rec + rec_off[p0 + i], rec_off[p0 + i + 1] - rec_off[p0 + i], opt_flags,
-                (rec_off[p0 + i] & 3) == 0);
+      read_head(head[i], R.head(p0 + i), R.extent(p0 + i), opt_flags, R.aligned(p0 + i));
       nok += head[i].ldsg_ok;
     }
     P.blk[(size_t)b].nok = nok;
@@ -374,12 +389,12 @@ void plan_chunk(Plan& P, const int32_t* rec, const int64_t* rec_off, int32_t p0,
     // slower under load)
     if (n_ok > 0 && (lm == dp::LDSG_ALWAYS || (lm == dp::LDSG_AUTO && n_ok + ldsg_busy <= dp::kLdsgMaxProblems))) {
       for (int32_t i = 0; i < n; ++i)
-        if (head[i].ldsg_ok) place_ldsg(head[i], rec + rec_off[p0 + i], (rec_off[p0 + i] & 3) == 0);
+        if (head[i].ldsg_ok) place_ldsg(head[i], R.head(p0 + i), R.aligned(p0 + i));
       P.n_ldsg = n_ok;
     }
   }
   // per block: totals and per-bucket counts / LDS maxima
-  const bool rec_aligned = ((uintptr_t)rec & 15) == 0;
+  const bool rec_aligned = R.base_aligned();
   over_blocks([&](int64_t b) {
     PlanBlock& B = P.blk[(size_t)b];
     const int32_t nok = B.nok;
@@ -390,7 +405,7 @@ void plan_chunk(Plan& P, const int32_t* rec, const int64_t* rec_off, int32_t p0,
       const Head& H = head[i];
       const bool d = rec_aligned && H.direct;
       B.ndirect += d;
-      B.other += d ? 0 : rec_off[p0 + i + 1] - rec_off[p0 + i];
+      B.other += d ? 0 : R.extent(p0 + i);
       if (H.place == M_LDS) {
         B.bcount[H.bucket]++;
         B.bmax[H.bucket] = std::max(B.bmax[H.bucket], H.lds);
@@ -491,7 +506,7 @@ void plan_chunk(Plan& P, const int32_t* rec, const int64_t* rec_off, int32_t p0,
     int mx = 0;
     Launch L{(int)P.order.size(), (int)bg.size(), mode, 0, false};
     for (int32_t i : bg) {
-      const int32_t* h = rec + rec_off[p0 + i];
+      const int32_t* h = R.head(p0 + i);
       L.dev_lists |= h[DP_H_FMT] == DP_FMT_I32 && !dp::device_watches(h);
       const Layout Y = mode == M_SPLIT    ? layout<M_SPLIT>(h)
                        : mode == M_SPLIT4 ? layout<M_SPLIT4>(h)
@@ -666,6 +681,11 @@ void plan_chunk(Plan& P, const int32_t* rec, const int64_t* rec_off, int32_t p0,
   if (pad_kb > 0)
     for (auto& L : P.launches)
       if (L.mode == M_LDS) L.lds = std::max(L.lds, pad_kb * 1024);
+}
+
+void plan_chunk(Plan& P, const int32_t* rec, const int64_t* rec_off, int32_t p0, int32_t n, int32_t opt_flags,
+                std::vector<uint8_t>* bad, Pool* pool = nullptr, int32_t ldsg_busy = 0) {
+  plan_chunk(P, RecSrc{rec, rec_off}, p0, n, opt_flags, bad, pool, ldsg_busy);
 }
 
 // Copy n words of s into d (narrowing or widening), checking lo <= x < hi
@@ -875,6 +895,7 @@ struct InLayout {
 struct OutLayout {
   size_t prob, installed, pool_len, pool, end;
   size_t d2h;  // bytes copied back by the pipelined D2H
+  size_t own_var = 0, own_con = 0;  // a fused chunk: the owner pairs of the cores, beside the pool
 };
 
 size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -890,7 +911,7 @@ InLayout in_layout(const Plan& P) {
   return L;
 }
 
-OutLayout out_layout(const Plan& P) {
+OutLayout out_layout(const Plan& P, bool owners = false) {
   OutLayout L;
   const size_t n = (size_t)P.n;
   size_t o = 0;
@@ -898,6 +919,10 @@ OutLayout out_layout(const Plan& P) {
   L.installed = o; o = al(o + (size_t)P.inst_off[n] * 4);
   L.pool_len = o;  o = al(o + 4);
   L.pool = o;      o = al(o + (size_t)std::max<int64_t>(P.core_cap, 1) * 4);
+  if (owners) {
+    L.own_var = o; o = al(o + (size_t)std::max<int64_t>(P.core_cap, 1) * 4);
+    L.own_con = o; o = al(o + (size_t)std::max<int64_t>(P.core_cap, 1) * 4);
+  }
   L.end = o;
   L.d2h = L.pool + (size_t)std::min<int64_t>(P.core_cap, kCoreWordsPerProblem * (int64_t)n) * 4;
   return L;
@@ -918,8 +943,12 @@ void fill_in_tables(const Plan& P, const InLayout& L, char* base) {
 // dp_result at global problems p0...  Cores come from the pool.
 // Returns the chunk's BCP-visited bytes.  One pass over the per-problem
 // results (in blocks on `pool` when given and the chunk is large).
+// With owners (a fused chunk), the cores' owner pairs go beside them into
+// own_var / own_con, indexed as res->core.  *core_words (may be null)
+// receives the core words delivered.
 uint64_t scatter(const Plan& P, const OutLayout& L, const char* out, int32_t p0, dp_result* res,
-                 dp::Pool* pool = nullptr) {
+                 dp::Pool* pool = nullptr, int32_t* own_var = nullptr, int32_t* own_con = nullptr,
+                 int64_t* core_words = nullptr) {
   const int32_t n = P.n;
   const dp::ProblemOut* po = reinterpret_cast<const dp::ProblemOut*>(out + L.prob);
   const uint32_t* inst = reinterpret_cast<const uint32_t*>(out + L.installed);
@@ -930,9 +959,16 @@ uint64_t scatter(const Plan& P, const OutLayout& L, const char* out, int32_t p0,
   static thread_local std::vector<uint64_t> part_tl;  // (per calling thread: no allocation once grown)
   std::vector<uint64_t>& part = part_tl;  // (a local name: the pool's threads write the caller's vector)
   part.assign((size_t)std::max(nb, 1), 0);
+  static thread_local std::vector<int64_t> cw_tl;
+  std::vector<int64_t>& cw = cw_tl;
+  cw.assign((size_t)std::max(nb, 1), 0);
+  const bool owners = own_var && own_con && L.own_var;
+  const int32_t* ovpool = reinterpret_cast<const int32_t*>(out + L.own_var);
+  const int32_t* ocpool = reinterpret_cast<const int32_t*>(out + L.own_con);
   auto block = [&](int64_t b) {
     const int32_t i0 = (int32_t)b * kBlock, i1 = std::min(n, i0 + kBlock);
     uint64_t bcp = 0;
+    int64_t words = 0;
     for (int32_t i = i0; i < i1; ++i) {
       const dp::ProblemOut& o = po[i];
       res->status[p0 + i] = o.status;
@@ -942,8 +978,13 @@ uint64_t scatter(const Plan& P, const OutLayout& L, const char* out, int32_t p0,
       bcp += o.bcp;
       if (o.core_len > 0) {
         const int64_t cap = res->core_off[p0 + i + 1] - res->core_off[p0 + i];
-        std::memcpy(res->core + res->core_off[p0 + i], cpool + o.core_at,
-                    (size_t)std::min<int64_t>(o.core_len, cap) * 4);
+        const size_t m = (size_t)std::min<int64_t>(o.core_len, cap);
+        std::memcpy(res->core + res->core_off[p0 + i], cpool + o.core_at, m * 4);
+        if (owners) {
+          std::memcpy(own_var + res->core_off[p0 + i], ovpool + o.core_at, m * 4);
+          std::memcpy(own_con + res->core_off[p0 + i], ocpool + o.core_at, m * 4);
+        }
+        words += (int64_t)m;
       }
       if (!same_inst) {  // a caller layout of its own: problem by problem
         const int64_t w = std::min(P.inst_off[(size_t)i + 1] - P.inst_off[(size_t)i],
@@ -956,11 +997,16 @@ uint64_t scatter(const Plan& P, const OutLayout& L, const char* out, int32_t p0,
       std::memcpy(res->installed + res->inst_off[p0] + w0, inst + w0, (size_t)(w1 - w0) * 4);
     }
     part[(size_t)b] = bcp;
+    cw[(size_t)b] = words;
   };
   if (pool && nb >= 4) pool->run(nb, std::function<void(int64_t)>(block), 1);
   else for (int32_t b = 0; b < nb; ++b) block(b);
   uint64_t bcp = 0;
   for (uint64_t x : part) bcp += x;
+  if (core_words) {
+    *core_words = 0;
+    for (int64_t x : cw) *core_words += x;
+  }
   for (size_t q = 0; q < P.skip.size(); ++q) {
     const int32_t i = P.skip[q];
     res->status[p0 + i] = DP_ERROR;
@@ -1065,6 +1111,7 @@ struct Lane {
   Spread spread;  // (DEPPY_SPREAD) its events; the sibling streams are set per chunk
   Buf h_in{nullptr, 0, true}, d_in, h_out{nullptr, 0, true}, d_out, scratch;
   bool zc_out = false;  // the chunk's kernels wrote their results straight into h_out
+  bool owners = false;  // a fused chunk: owner pairs beside the core pool (ol.own_var / own_con)
   // the chunk in flight
   dp_job* job = nullptr;
   int32_t p0 = 0;
@@ -1141,6 +1188,11 @@ struct dp_job {
   const int32_t* rec = nullptr;
   const int64_t* rec_off = nullptr;
   bool pinned = false;  // the records are page-locked (pinned_range)
+  // a fused job (dp::submit_job): the records lie in device memory, rec is
+  // null and the plan reads fs.heads; one chunk, on the context's first device
+  bool fused = false;
+  dp::FusedSrc fs{};
+  int64_t *h2d_acc = nullptr, *d2h_acc = nullptr;  // byte accounting (under m)
   dp_result res{};
   // completion: chunks not yet delivered; the waiter sleeps on cv
   std::mutex m;
@@ -1306,6 +1358,8 @@ void set_siblings(const Device& D, int i, Spread& sp, bool on) {
   for (int j = 1; j < D.nstreams && sp.n < kMaxSpread; ++j) sp.s[sp.n++] = D.lanes[(i + j) % D.nstreams].s;
 }
 
+void account(dp_job* job, int64_t h2d, int64_t d2h);
+
 // Wait for a lane's chunk and scatter its results into its job's dp_result
 // (the job's bookkeeping is deliver()'s).
 int finish_lane(dp_ctx* ctx, Device& D, Lane& L) {
@@ -1329,6 +1383,7 @@ int finish_lane(dp_ctx* ctx, Device& D, Lane& L) {
     HIP_OK(hipMemcpyAsync(L.h_out.p + L.ol.d2h, L.d_out.p + L.ol.d2h, need - L.ol.d2h, hipMemcpyDeviceToHost, L.s));
     HIP_OK(hipStreamSynchronize(L.s));
     st.d2h_bytes += (int64_t)(need - L.ol.d2h);
+    account(job, 0, (int64_t)(need - L.ol.d2h));
   }
   add_device_stats(D, st);
   // the results to the caller on the finisher thread, so the worker goes on
@@ -1345,6 +1400,14 @@ int finish_lane(dp_ctx* ctx, Device& D, Lane& L) {
 }
 
 void chunk_done(dp_job* job, int rc);
+
+// Bytes a chunk of `job` moved over PCIe, for a job that keeps count.
+void account(dp_job* job, int64_t h2d, int64_t d2h) {
+  if (!job->h2d_acc && !job->d2h_acc) return;
+  std::lock_guard<std::mutex> lk(job->m);
+  if (job->h2d_acc) *job->h2d_acc += h2d;
+  if (job->d2h_acc) *job->d2h_acc += d2h;
+}
 
 // Wait until lane L's results are scattered (the worker, before it reuses
 // the lane's buffers or plan).
@@ -1370,8 +1433,19 @@ void finisher_main(dp_ctx* ctx, Device* Dp) {
     dp_stats st{};
     const double t0 = now_ms();
     dp_job* job = L->fjob;
-    st.bcp_bytes += (int64_t)scatter(L->plan, L->ol, L->h_out.p, L->p0, &job->res, D.fpool);
+    int64_t core_words = 0;
+    st.bcp_bytes += (int64_t)scatter(L->plan, L->ol, L->h_out.p, L->p0, &job->res, D.fpool,
+                                     L->owners ? job->fs.core_var : nullptr, L->owners ? job->fs.core_con : nullptr,
+                                     &core_words);
     st.scatter_ms += now_ms() - t0;
+    if (L->zc_out) {
+      // results written through mapped host memory: what the kernels wrote
+      // (and, for the owners kernel, read back) crossed PCIe
+      const int64_t launched = (int64_t)L->plan.order.size();
+      const int64_t fixed = launched * (int64_t)sizeof(dp::ProblemOut) + 4 * L->plan.inst_off[(size_t)L->plan.n];
+      account(job, L->owners ? launched * (int64_t)sizeof(dp::ProblemOut) + 4 * core_words : 0,
+              fixed + 4 * core_words * (L->owners ? 3 : 1));
+    }
     add_device_stats(D, st);
     lk.lock();
     L->scattering = false;
@@ -1486,7 +1560,10 @@ int grow_device_lanes(dp_ctx* ctx, Device& D, Lane& L, const LaneNeed& need) {
 }
 
 // Stage and enqueue problems [p0, p0+n) of a job on lane L.
+int start_fused_chunk(dp_ctx* ctx, Device& D, Lane& L, dp_job* job, int32_t p0, int32_t n);
 int start_chunk(dp_ctx* ctx, Device& D, Lane& L, dp_job* job, int32_t p0, int32_t n) {
+  if (job->fused) return start_fused_chunk(ctx, D, L, job, p0, n);
+  L.owners = false;
   HIP_OK(hipSetDevice(L.device));
   dp_stats st{};
   const int64_t allocs0 = g_buf_allocs.load(std::memory_order_relaxed);
@@ -1629,7 +1706,96 @@ int start_chunk(dp_ctx* ctx, Device& D, Lane& L, dp_job* job, int32_t p0, int32_
   st.problems += n;
   st.h2d_bytes += (int64_t)h2d;
   st.d2h_bytes += L.zc_out ? 0 : (int64_t)L.ol.d2h;
+  account(job, (int64_t)h2d, L.zc_out ? 0 : (int64_t)L.ol.d2h);
   st.rec_bytes += P.rec_bytes;
+  st.allocs += g_buf_allocs.load(std::memory_order_relaxed) - allocs0 + (L.bad.capacity() != bad_cap) +
+               (plan_cap(L.plan) != plan_cap0);
+  add_device_stats(D, st);
+  return 0;
+}
+
+// A fused job's chunk (dp::submit_job with a FusedSrc): the records already
+// lie in device memory where the lowering left them, so the plan is made from
+// their headers, every launched problem is "direct" at its record's own
+// offset, and only the tables (work items, the pool's counter, scratch
+// offsets) go to the device.  The results come back through mapped host
+// memory whatever the context's setting, and the owners kernel follows the
+// solve launches on the lane's stream.  On an error after the first enqueue
+// the lane's streams are synchronised before the chunk is reported failed.
+int enqueue_fused_chunk(dp_ctx* ctx, Device& D, Lane& L, dp_job* job, int32_t p0, int32_t n, const InLayout& il,
+                        dp_stats& st) {
+  const dp::FusedSrc& F = job->fs;
+  const Plan& P = L.plan;
+  hipStream_t cs = L.cs ? L.cs : L.s;
+  HIP_OK(hipMemcpyAsync(L.d_in.p, L.h_in.p, il.end, hipMemcpyHostToDevice, cs));
+  if (cs != L.s) {
+    HIP_OK(hipEventRecord(L.copied, cs));
+    HIP_OK(hipStreamWaitEvent(L.s, L.copied, 0));
+  }
+  D.last_copied = nullptr;
+  dp::KernelArgs a = kernel_args(il, L.ol, L.d_in.p, L.h_out.dev, reinterpret_cast<int32_t*>(L.scratch.p),
+                                 ctx->budget);
+  a.rec = F.dev_rec;
+  a.core_pool_len = at<int32_t>(L.d_in.p, il.pool_len);  // (zeroed by the copy above)
+  HIP_OK(hipEventRecord(L.k0, L.s));
+  set_siblings(D, (int)(&L - D.lanes) % D.nstreams, L.spread, ctx->spread);
+  if (enqueue_launches(ctx, P, a, L.s, st, &L.spread)) return -1;
+  HIP_OK(dp::launch_core_owners(a.items, (int)P.order.size(), a.out, a.core, std::max<int64_t>(P.core_cap, 1),
+                                at<int32_t>(L.h_out.dev, L.ol.own_var), at<int32_t>(L.h_out.dev, L.ol.own_con),
+                                F.dev_nid + p0, F.dev_ivs + (int64_t)p0 * F.owner_stride,
+                                F.dev_ics + (int64_t)p0 * F.owner_stride, F.owner_stride, L.s));
+  HIP_OK(hipEventRecord(L.k1, L.s));
+  HIP_OK(hipEventRecord(L.done, L.s));
+  (void)n;
+  return 0;
+}
+
+int start_fused_chunk(dp_ctx* ctx, Device& D, Lane& L, dp_job* job, int32_t p0, int32_t n) {
+  HIP_OK(hipSetDevice(L.device));
+  dp_stats st{};
+  const dp::FusedSrc& F = job->fs;
+  const int64_t allocs0 = g_buf_allocs.load(std::memory_order_relaxed);
+  const size_t bad_cap = L.bad.capacity(), plan_cap0 = plan_cap(L.plan);
+  const double t0 = now_ms();
+  L.bad.assign((size_t)n, 0);
+  int32_t ldsg_busy = 0;
+  for (const Lane* o : D.inflight) ldsg_busy += o->plan.n_ldsg;
+  dp::plan_chunk(L.plan, dp::RecSrc{nullptr, F.rec_off, F.heads}, p0, n, ctx->flags, &L.bad, D.pool, ldsg_busy);
+  const double t_plan = now_ms();
+  st.plan_ms += t_plan - t0;
+  Plan& Q = L.plan;
+  for (int32_t i = 0; i < n; ++i) {
+    // (the lowering kernel emits the staged forms only: anything else cannot
+    // be staged from here, and is an error rather than another path)
+    if (Q.head[(size_t)i].place >= 0 && !Q.direct[(size_t)i]) {
+      t_err = "dp_lower_solve: a device-lowered record is not in a staged form for its placement";
+      return -1;
+    }
+    Q.dev_off[(size_t)i] = F.rec_off[p0 + i];
+  }
+  Q.img_words = 0;  // no image: the kernels read F.dev_rec
+  const InLayout il = in_layout(Q);
+  L.ol = out_layout(Q, true);
+  const LaneNeed need{il.end, il.end, L.ol.end, 0, (size_t)std::max<int64_t>(Q.scratch_words, 1) * 4};
+  if (!need.fits(L) && grow_device_lanes(ctx, D, L, need)) return -1;
+  fill_in_tables(Q, il, L.h_in.p);
+  st.stage_ms += now_ms() - t_plan;
+  L.zc_out = true;
+  L.owners = true;
+  if (enqueue_fused_chunk(ctx, D, L, job, p0, n, il, st)) {
+    (void)hipStreamSynchronize(L.s);
+    if (L.cs) (void)hipStreamSynchronize(L.cs);
+    for (int k = 0; k < L.spread.n; ++k) (void)hipStreamSynchronize(L.spread.s[k]);
+    return -1;
+  }
+  L.job = job;
+  L.p0 = p0;
+  st.chunks++;
+  st.problems += n;
+  st.h2d_bytes += (int64_t)il.end;
+  account(job, (int64_t)il.end, 0);
+  st.rec_bytes += Q.rec_bytes;
+  st.direct_chunks++;
   st.allocs += g_buf_allocs.load(std::memory_order_relaxed) - allocs0 + (L.bad.capacity() != bad_cap) +
                (plan_cap(L.plan) != plan_cap0);
   add_device_stats(D, st);
@@ -1809,6 +1975,7 @@ int lane_streams() {
 
 namespace dp {
 int ctx_first_ordinal(const dp_ctx* ctx) { return ctx && !ctx->dev.empty() ? ctx->dev[0].ordinal : -1; }
+int32_t ctx_flags(const dp_ctx* ctx) { return ctx ? ctx->flags : 0; }
 }  // namespace dp
 
 extern "C" {
@@ -1997,6 +2164,17 @@ int dp_plan_order(const dp_batch* b, int32_t opt_flags, int32_t* order, int32_t*
   return (int)P.launches.size();
 }
 
+int dp_plan_order_heads(const int32_t* heads, const int64_t* rec_off, int32_t n, int32_t opt_flags, int32_t* order,
+                        int32_t* launch_first) {
+  if (!order || n < 0 || (n > 0 && (!heads || !rec_off))) return -1;
+  static thread_local Plan P;
+  dp::plan_chunk(P, dp::RecSrc{nullptr, rec_off, heads}, 0, n, opt_flags, nullptr, &dp::host_pool());
+  std::copy(P.order.begin(), P.order.end(), order);
+  if (launch_first)
+    for (size_t k = 0; k < P.launches.size(); ++k) launch_first[k] = P.launches[k].first;
+  return (int)P.launches.size();
+}
+
 int dp_plan_placements(const dp_batch* b, int32_t opt_flags, int8_t* place) {
   if (!b || !place || b->n_problems < 0 || (b->n_problems > 0 && (!b->rec || !b->rec_off))) return -1;
   static thread_local Plan P;  // (reused, as a lane's: no allocation once grown)
@@ -2040,14 +2218,41 @@ int dp_lds_occupancy(int32_t lds_bytes, int32_t capped) { return dp::lds_occupan
 // ---- host-to-host pipeline ----
 
 int dp_submit(dp_ctx* ctx, const dp_batch* b, dp_result* res, dp_job** out) {
-  if (!ctx || !b || !res || !out || b->n_problems < 0 || (b->n_problems > 0 && (!b->rec || !b->rec_off)))
+  return dp::submit_job(ctx, b, res, nullptr, nullptr, nullptr, out);
+}
+
+}  // extern "C"
+
+int dp::submit_job(dp_ctx* ctx, const dp_batch* b, dp_result* res, const dp::FusedSrc* fused, int64_t* h2d,
+                   int64_t* d2h, dp_job** out) {
+  if (!ctx || !b || !res || !out || b->n_problems < 0 ||
+      (b->n_problems > 0 && ((!fused && !b->rec) || !b->rec_off)))
     return -1;
   auto* job = new dp_job;
   job->n = b->n_problems;
   job->rec = b->rec;
   job->rec_off = b->rec_off;
-  job->pinned = ctx->direct && job->n > 0 && pinned_range(b->rec, 4 * (size_t)b->rec_off[job->n]);
+  job->h2d_acc = h2d;
+  job->d2h_acc = d2h;
   job->res = *res;
+  if (fused) {  // one chunk, on the device the records lie on
+    job->fused = true;
+    job->fs = *fused;
+    job->rec = nullptr;
+    job->rec_off = fused->rec_off;
+    job->chunks_left = job->n > 0 ? 1 : 0;
+    if (job->n > 0) {
+      Device& D = ctx->dev[0];
+      {
+        std::lock_guard<std::mutex> lk(D.qmu);
+        D.q.push_back(Task{job, 0, job->n});
+      }
+      D.qcv.notify_one();
+    }
+    *out = job;
+    return 0;
+  }
+  job->pinned = ctx->direct && job->n > 0 && pinned_range(b->rec, 4 * (size_t)b->rec_off[job->n]);
   std::vector<std::pair<int32_t, int32_t>> chunks;
   cut_chunks(ctx, job, chunks);
   job->chunks_left = (int)chunks.size();
@@ -2079,6 +2284,8 @@ int dp_submit(dp_ctx* ctx, const dp_batch* b, dp_result* res, dp_job** out) {
   *out = job;
   return 0;
 }
+
+extern "C" {
 
 int dp_job_wait(dp_ctx* ctx, dp_job* job) {
   if (!ctx || !job) return -1;

@@ -531,6 +531,43 @@ def solve_wire(wire, context: Optional[_lib.Context] = None, trace_cap: int = 0)
     return lw, res
 
 
+class _FusedLowering:
+    """What SolveBatch reads of a lowering (errors and their texts), from a
+    fused solve: the identities' owners come with the cores instead."""
+
+    def __init__(self, res: dict):
+        self.n = len(res["err"])
+        self.err = res["err"]
+        self.msg = res["msg"]
+
+
+def _device_lowerer(ctx: _lib.Context) -> "_lib.DeviceLowerer":
+    dls = getattr(_lowering, "dl", None)
+    if dls is None:
+        dls = _lowering.dl = {}
+    dl = dls.get(id(ctx))
+    if dl is None or dl.ctx is not ctx:
+        dl = dls[id(ctx)] = _lib.DeviceLowerer(ctx)
+    return dl
+
+
+def solve_wire_fused(w32: "_lib.Wire32Arrays", context: Optional[_lib.Context] = None):
+    """solve_wire's results from the compact wire with the lowering's records
+    and owners left on the device (dp_lower_solve): (lowering, results), where
+    results also holds core_var / core_con, the AppliedConstraint of every
+    core identity, and the call's PCIe bytes.  The arrays are the device
+    lowering's own: valid until this thread's next fused call on the context."""
+    with (contextlib.nullcontext() if context else _ctx_lock):
+        ctx = context or device_context()
+        if getattr(_lowering, "busy", 0) > 1:  # inside this thread's SolveBatch: storage of its own
+            dl = _lib.DeviceLowerer(ctx)
+            res = {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in dl.lower_solve(w32).items()}
+            dl.close()
+        else:
+            res = _device_lowerer(ctx).lower_solve(w32)
+    return _FusedLowering(res), res
+
+
 class _Stitched:
     """The lowering outputs SolveBatch reads (identities, errors), gathered
     from the sub-batches of a pipelined solve (copies: the sub-batches'
@@ -597,8 +634,12 @@ def _solve_pipelined(wire: _lib.WireArrays, context: Optional[_lib.Context]):
 
 
 def SolveBatch(inputs: Sequence[Sequence[Variable]], tracer: Optional[Tracer] = None,
-               context: Optional[_lib.Context] = None) -> list:
+               context: Optional[_lib.Context] = None, fused: bool = False) -> list:
     """Solve many independent problems in one GPU launch.
+
+    fused=True (without a tracer, and when the batch fits the compact 32-bit
+    wire) lowers on the GPU and solves the records where they lie
+    (solve_wire_fused); the results are the same.
 
     With a tracer other than DefaultTracer the GPU records every
     unsatisfiable search step and the steps are replayed through
@@ -612,13 +653,23 @@ def SolveBatch(inputs: Sequence[Sequence[Variable]], tracer: Optional[Tracer] = 
         return out
     _lowering.busy = getattr(_lowering, "busy", 0) + 1
     try:
-        return _solve_batch(inputs, tracer, traced, context, out)
+        return _solve_batch(inputs, tracer, traced, context, out, fused and not traced)
     finally:
         _lowering.busy -= 1
 
 
-def _solve_batch(inputs, tracer, traced, context, out) -> list:
-    lw, res = solve_wire(encode_inputs(inputs), context, TRACE_CAP if traced else 0)
+def _solve_batch(inputs, tracer, traced, context, out, fused=False) -> list:
+    wire = encode_inputs(inputs)
+    w32 = None
+    if fused:
+        try:
+            w32 = _lib.Wire32Arrays(wire)
+        except ValueError:  # does not fit 32 bits: the 64-bit wire's path
+            w32 = None
+    if w32 is not None:
+        lw, res = solve_wire_fused(w32, context)
+    else:
+        lw, res = solve_wire(wire, context, TRACE_CAP if traced else 0)
     retraced = {}
     if traced:
         with (contextlib.nullcontext() if context else _ctx_lock):
@@ -655,11 +706,16 @@ def _solve_batch(inputs, tracer, traced, context, out) -> list:
             inst = _lib.installed_list(res, p, len(variables))
             out[p] = ([variables[v] for v in inst] or None, None)
         elif st == UNSAT:
-            i0 = int(lw.ident_off[p])
             applied = []
-            for ident in _lib.core_list(res, p):
-                vi = int(lw.ident_var[i0 + ident])
-                ci = int(lw.ident_con[i0 + ident])
+            if w32 is not None:
+                c0 = int(res["core_off"][p])
+                owners = [(int(res["core_var"][c0 + k]), int(res["core_con"][c0 + k]))
+                          for k in range(int(res["core_len"][p]))]
+            else:
+                i0 = int(lw.ident_off[p])
+                owners = [(int(lw.ident_var[i0 + ident]), int(lw.ident_con[i0 + ident]))
+                          for ident in _lib.core_list(res, p)]
+            for vi, ci in owners:
                 var = variables[vi]
                 applied.append(AppliedConstraint(var, var.Constraints()[ci]))
             out[p] = (None, NotSatisfiable(applied))

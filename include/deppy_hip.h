@@ -417,6 +417,47 @@ void dp_dlower_free(dp_dlower* d);
 int dp_lower_device(dp_dlower* d, const dp_wire32* wire, int32_t flags, dp_lowered* lw);
 /* Problems of the last dp_lower_device call lowered on the host. */
 int64_t dp_dlower_host_count(const dp_dlower* d);
+
+/* Fused lowering and solve: the compact wire in, results out.  The device
+ * lowering leaves every record in device memory where its kernel wrote it,
+ * and the solve reads it there: nothing of the lowering crosses PCIe but each
+ * record's 16-word header and two counts (what the host needs to plan the
+ * launches), and the owners of the NotSatisfiable explanations that were
+ * reported, which a kernel looks up on the device.  The batch is processed in
+ * windows of at most 16,384 problems (DEPPY_FUSED_WINDOW, read per call), so
+ * the device scratch is bounded whatever the batch size, and one window's
+ * lowering runs under the previous one's solve.  Problems the lowering kernel
+ * leaves to the host (see dp_lower_device) are lowered there with
+ * DP_LOWER_NARROW | DP_LOWER_PACKED | DP_LOWER_PINNED and solved as an
+ * ordinary job beside the fused windows; when they hold most of the batch,
+ * the whole call is host lowering plus that job.  The fused windows run on
+ * the context's first device only: sharding one wire over several devices is
+ * out of scope.  The context must outlive the dp_dlower. */
+typedef struct dp_solved {      /* arrays owned by the dp_dlower, page-locked, valid until its next call */
+  int32_t n_problems;
+  const int32_t* err;           /* [P] enum dp_lower_err */
+  const int8_t* status; const int32_t* flags; const int64_t* steps;   /* [P] */
+  const uint32_t* installed; const int64_t* inst_off;                 /* as dp_result / dp_result_layout */
+  const int32_t* core_len; const int64_t* core_off;                   /* capacity nid per problem */
+  const int32_t* core;          /* identities, as dp_result.core */
+  const int32_t* core_var;      /* owner of core[k]: variable index ... */
+  const int32_t* core_con;      /* ... and index in that variable's Constraints() */
+  int64_t h2d_bytes, d2h_bytes; /* every byte this call moved over PCIe in each direction;
+                                   results the kernels write through mapped host memory count as d2h */
+  int64_t host_lowered;         /* problems lowered on the host */
+} dp_solved;
+/* For every problem exactly what dp_lower_into with the flags above and
+ * dp_solve give on the same problems from the 64-bit wire, and
+ * core_var / core_con[core_off[p] + k] = ident_var / ident_con[ident_off[p] +
+ * core[core_off[p] + k]].  A problem with a lowering error has that err, the
+ * reference's text (dp_dlower_error) and an empty record's result; a
+ * malformed wire fails the whole call.  Synchronous.  Returns 0, or -1 (text
+ * in dp_last_global_error()); NULL arguments return -1 without touching a
+ * device. */
+int dp_lower_solve(dp_dlower* d, const dp_wire32* wire, dp_solved* out);
+/* enum dp_lower_err of problem p of the last dp_lower_solve; *msg (may be
+ * NULL) receives the reference's error text. */
+int32_t dp_dlower_error(const dp_dlower* d, int32_t p, const char** msg);
 /* Page-locked host memory for wire batches (the H2D copy then runs by DMA
  * from where they lie).  NULL without a device. */
 void* dp_host_alloc(int64_t bytes);
@@ -661,6 +702,12 @@ int dp_lds_occupancy(int32_t lds_bytes, int32_t capped);
  *     launch after launch) and launch_first[] (each launch's first index
  *     into order; up to 21 launches).  Returns the number of launches or -1. */
 int dp_plan_order(const dp_batch* b, int32_t opt_flags, int32_t* order, int32_t* launch_first);
+/*   dp_plan_order_heads: the same plan from the records' headers alone:
+ *     heads[n][DP_H_SIZE] (record i's header) and rec_off[n+1] (the records'
+ *     extents and alignment), as the fused path plans records that stay in
+ *     device memory. */
+int dp_plan_order_heads(const int32_t* heads, const int64_t* rec_off, int32_t n, int32_t opt_flags,
+                        int32_t* order, int32_t* launch_first);
 
 /* Device time of the solve kernel(s) of the last waited launch (dp_run,
  * dp_wait, dp_solve), measured with HIP events on its stream (max over devices). */
