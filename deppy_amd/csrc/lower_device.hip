@@ -821,11 +821,29 @@ struct MapBuf {
   }
 };
 
+// The device copy of one range of a wire's problems and the lowering's
+// outputs for it (a slot and the identity owners per problem).
+struct WireStage {
+  DevBuf<int32_t> pvo, pco, pao, vid, ckn, arg, words, nid, slots, ivs, ics;
+  DevBuf<uint16_t> vnc, cna, vid16, arg16;
+  hipError_t reserve(size_t n, size_t nvars, size_t ncons, size_t nargs, bool ids16) {
+    hipError_t e = hipSuccess;
+    auto ok = [&e](hipError_t r) { return (e = r) == hipSuccess; };
+    (void)(ok(pvo.need(n + 1)) && ok(pco.need(n + 1)) && ok(pao.need(n + 1)) &&
+           (ids16 ? ok(vid16.need(nvars + 1)) && ok(arg16.need(nargs + 1))
+                  : ok(vid.need(nvars + 1)) && ok(arg.need(nargs + 1))) &&
+           ok(vnc.need(nvars + 1)) && ok(ckn.need(ncons + 1)) && ok(cna.need(ncons + 1)) && ok(words.need(n)) &&
+           ok(nid.need(n)) && ok(slots.need(n * DL_SLOT)) && ok(ivs.need(n * DL_C)) && ok(ics.need(n * DL_C)));
+    return e;
+  }
+  template <class F>
+  int64_t enqueue(dp_dlower* d, const dp_wire32* w, int32_t q0, int32_t q1, F after_piece);
+};
+
 // One window of the fused path: the window's wire ranges, its slots and
 // owners on the device, its headers on the host, and the job solving it.
 struct FusedWin {
-  DevBuf<int32_t> pvo, pco, pao, vid, ckn, arg, words, nid, slots, ivs, ics;
-  DevBuf<uint16_t> vnc, cna, vid16, arg16;
+  WireStage wire;
   MapBuf heads, counts;
   hipEvent_t lowered = nullptr;
   dp_job* job = nullptr;
@@ -863,6 +881,43 @@ struct CoreSet {
   }
 };
 
+// One result layout in page-locked memory: the arrays a dp_result points
+// into and the cores' owners.
+struct ResultStage {
+  PinBuf<int8_t> status;
+  PinBuf<int32_t> flags, core_len;
+  PinBuf<int64_t> steps, inst_off, core_off;
+  PinBuf<uint32_t> inst;
+  CoreSet core;
+  // The offsets of n problems and (rows) their status, flags, steps and
+  // core_len; then, once the offsets are known, what they index.
+  bool need(size_t n, bool rows = true) {
+    return inst_off.need(n + 1) && core_off.need(n + 1) &&
+           (!rows || (status.need(n) && flags.need(n) && steps.need(n) && core_len.need(n)));
+  }
+  bool need_data(size_t inst_words, size_t cores) { return inst.need(inst_words + 1) && core.need(cores + 1); }
+  dp_result at(int64_t p) {  // problems p.. as a batch of their own
+    dp_result r{};
+    r.status = status.p + p;
+    r.flags = flags.p + p;
+    r.steps = steps.p + p;
+    r.core_len = core_len.p + p;
+    r.installed = inst.p;
+    r.inst_off = inst_off.p + p;
+    r.core = core.core.p;
+    r.core_off = core_off.p + p;
+    return r;
+  }
+  void publish(dp_solved* out) const {
+    out->inst_off = inst_off.p;
+    out->core_off = core_off.p;
+    out->installed = inst.p;
+    out->core = core.core.p;
+    out->core_var = core.cvar.p;
+    out->core_con = core.ccon.p;
+  }
+};
+
 constexpr int32_t kFusedWindow = 16384;  // problems per window: 320 MiB of slots and owners at most
 
 }  // namespace
@@ -870,20 +925,16 @@ constexpr int32_t kFusedWindow = 16384;  // problems per window: 320 MiB of slot
 struct dp_dlower {
   int dev = 0;
   dp_ctx* ctx = nullptr;  // dp_lower_solve submits its jobs to it
-  // -- dp_lower_solve --
+  // The two windows of dp_lower_solve.  dp_lower_device stages in fw[0].wire:
+  // one call runs at a time, and dp_lower_solve leaves no job behind.
   FusedWin fw[2];
   std::vector<int64_t> f_rec_off;  // [window + 1]: slot i at i * DL_SLOT
-  PinBuf<int32_t> o_err, o_flags, o_core_len;
-  PinBuf<int8_t> o_status;
-  PinBuf<int64_t> o_steps;
-  // the fused windows' layout (a problem left to the host takes no room),
-  // the host-lowered problems' own, and the two merged by problem index
-  PinBuf<int64_t> v_inst_off, v_core_off, s_inst_off, s_core_off, m_inst_off, m_core_off;
-  PinBuf<uint32_t> v_inst, s_inst, m_inst;
-  CoreSet v_core, s_core, m_core;
-  PinBuf<int32_t> s_flags, s_core_len;
-  PinBuf<int8_t> s_status;
-  PinBuf<int64_t> s_steps;
+  // -- dp_lower_solve --
+  PinBuf<int32_t> o_err;
+  // the fused windows' results (a problem left to the host takes no room; its
+  // per-problem rows are the call's), the host-lowered problems' own, and the
+  // layout of the two merged by problem index
+  ResultStage v, s, m;
   dp_lowered* side = nullptr;   // the host-lowered problems' records
   std::vector<int32_t> f_which;  // the problems of the last dp_lower_solve lowered on the host (ascending)
   std::vector<int32_t> f_err;    // their enum dp_lower_err
@@ -892,11 +943,10 @@ struct dp_dlower {
   hipStream_t pst = nullptr;  // the packing (its writes to host memory run under the next piece's lowering)
   static constexpr int kMaxPieces = 8;
   hipEvent_t ev[kMaxPieces] = {}, es[kMaxPieces] = {};
-  DevBuf<int32_t> pvo, pco, pao, vid, ckn, arg, words, nid, slots, ivs, ics, rec, ivar, icon;
-  DevBuf<uint16_t> vnc, cna, vid16, arg16;
+  // -- dp_lower_device: the packed batch and its offsets --
+  DevBuf<int32_t> rec, ivar, icon;
   DevBuf<int64_t> ro, io;
-  int64_t* h_off = nullptr;  // page-locked: rec_off then ident_off
-  size_t h_cap = 0;
+  PinBuf<int64_t> h_off;  // rec_off then ident_off
   int64_t host_count = 0;
   // the problems lowered on the host, as a dp_wire of their own
   std::vector<int32_t> which;
@@ -907,7 +957,6 @@ struct dp_dlower {
   std::mutex mu;  // one call at a time
   ~dp_dlower() {
     if (side) dp_lowered_free(side);
-    if (h_off) dp::pinned_free(h_off);
     for (auto e : ev)
       if (e) (void)hipEventDestroy(e);
     for (auto e : es)
@@ -920,14 +969,109 @@ struct dp_dlower {
 
 namespace {
 std::string hip_err(const char* what, hipError_t e) { return std::string("dp_lower_device: ") + what + ": " + hipGetErrorString(e); }
-#define DL_OK(expr)                                  \
+#define DL_OK_OR(expr, cleanup)                      \
   do {                                               \
     const hipError_t e_ = (expr);                    \
     if (e_ != hipSuccess) {                          \
+      cleanup;                                       \
       dp::set_global_error(hip_err(#expr, e_));      \
       return -1;                                     \
     }                                                \
   } while (0)
+#define DL_OK(expr) DL_OK_OR(expr, (void)0)
+
+int dl_fail(const char* text) {
+  dp::set_global_error(text);
+  return -1;
+}
+
+// Before an error returns once anything has been enqueued: nothing is left
+// running on the lowerer's streams.
+void drain(dp_dlower* d) {
+  (void)hipStreamSynchronize(d->cst);
+  (void)hipStreamSynchronize(d->st);
+  (void)hipStreamSynchronize(d->pst);
+}
+#define DL_OK_DRAIN(expr) DL_OK_OR(expr, drain(d))
+
+// Enqueue the copy and the lowering of w's problems [q0, q1) into this stage,
+// the range as a batch of its own (offsets from its first element).  Behind
+// each piece [r0, r1)'s lowering, after_piece(r0, r1) enqueues what the
+// caller has to follow it and returns a hipError_t.  Returns the bytes copied
+// to the device, or -1.
+template <class F>
+int64_t WireStage::enqueue(dp_dlower* d, const dp_wire32* w, int32_t q0, int32_t q1, F after_piece) {
+  const int32_t n = q1 - q0;
+  const int32_t pv0 = w->prob_var_off[q0], cb0 = w->prob_con_off[q0], ab0 = w->prob_arg_off[q0];
+  const int32_t nvars = w->prob_var_off[q1] - pv0, ncons = w->prob_con_off[q1] - cb0,
+                nargs = w->prob_arg_off[q1] - ab0;
+  const bool ids16 = w->var_id16 != nullptr;
+  DL_OK(reserve((size_t)n, (size_t)nvars, (size_t)ncons, (size_t)nargs, ids16));
+  hipStream_t st = d->st, cst = d->cst;
+  int64_t bytes = 0;
+  auto h2d = [&](auto* dst, const auto* src, int64_t m) {
+    bytes += m > 0 ? m * (int64_t)sizeof(*src) : 0;
+    return m > 0 ? hipMemcpyAsync(dst, src, (size_t)m * sizeof(*src), hipMemcpyHostToDevice, cst) : hipSuccess;
+  };
+  DL_OK(h2d(pvo.p, w->prob_var_off + q0, (int64_t)n + 1));
+  DL_OK(h2d(pco.p, w->prob_con_off + q0, (int64_t)n + 1));
+  DL_OK(h2d(pao.p, w->prob_arg_off + q0, (int64_t)n + 1));
+  DlArgs a{};
+  a.pvo = pvo.p;
+  a.pco = pco.p;
+  a.pao = pao.p;
+  a.vid = vid.p;
+  a.vnc = vnc.p;
+  a.ckn = ckn.p;
+  a.cna = cna.p;
+  a.arg = arg.p;
+  a.vid16 = vid16.p;
+  a.arg16 = arg16.p;
+  a.ids16 = ids16 ? 1 : 0;
+  a.pbase = pv0;
+  a.cbase = cb0;
+  a.abase = ab0;
+  a.nvars = nvars;
+  a.ncons = ncons;
+  a.nargs = nargs;
+  a.n_strs = w->n_strs;
+  a.group_above = dp::group_above();
+  a.words = words.p;
+  a.nid = nid.p;
+  a.slots = slots.p;
+  a.ivs = ivs.p;
+  a.ics = ics.p;
+  // pieces: the wire's copy of piece k+1 runs under the lowering (and what
+  // follows it) of piece k.  Every copy and its event is enqueued first: an
+  // event marker may share a hardware queue with the packing's stream, and
+  // one enqueued after pack(k) would hold lower(k+1) behind it.
+  const int pieces = (int)std::min<int64_t>(dp_dlower::kMaxPieces, std::max<int64_t>(1, n / 2048));
+  auto piece = [&](int k) { return q0 + (int32_t)((int64_t)n * k / pieces); };
+  for (int k = 0; k < pieces; ++k) {
+    const int32_t r0 = piece(k), r1 = piece(k + 1);
+    const int32_t v0 = w->prob_var_off[r0], v1 = w->prob_var_off[r1];
+    const int32_t c0 = w->prob_con_off[r0], c1 = w->prob_con_off[r1];
+    const int32_t x0 = w->prob_arg_off[r0], x1 = w->prob_arg_off[r1];
+    if (ids16) DL_OK(h2d(vid16.p + (v0 - pv0), w->var_id16 + v0, v1 - v0));
+    else DL_OK(h2d(vid.p + (v0 - pv0), w->var_id + v0, v1 - v0));
+    DL_OK(h2d(vnc.p + (v0 - pv0), w->var_ncon + v0, v1 - v0));
+    DL_OK(h2d(ckn.p + (c0 - cb0), w->con_kn + c0, c1 - c0));
+    DL_OK(h2d(cna.p + (c0 - cb0), w->con_nargs + c0, c1 - c0));
+    if (ids16) DL_OK(h2d(arg16.p + (x0 - ab0), w->con_arg16 + x0, x1 - x0));
+    else DL_OK(h2d(arg.p + (x0 - ab0), w->con_arg + x0, x1 - x0));
+    DL_OK(hipEventRecord(d->ev[k], cst));
+  }
+  for (int k = 0; k < pieces; ++k) {
+    const int32_t r0 = piece(k), r1 = piece(k + 1);
+    DL_OK(hipStreamWaitEvent(st, d->ev[k], 0));
+    if (r1 == r0) continue;
+    a.p0 = r0 - q0;
+    hipLaunchKernelGGL(lower_kernel, dim3((unsigned)(r1 - r0)), dim3(DL_T), 0, st, a);
+    DL_OK(hipGetLastError());
+    DL_OK(after_piece(r0, r1));
+  }
+  return bytes;
+}
 
 // The problems d->which of w as a dp_wire of their own (64-bit, offsets
 // from 0).  Inconsistent counts stay malformed (a negative identifier), so
@@ -1066,6 +1210,26 @@ bool monotone(const int32_t* o, int32_t P) {
     if (o[p + 1] < o[p]) return false;
   return true;
 }
+
+// The batch-level shape of a compact wire.  WIRE_OFFSETS: an offset array is
+// missing or not monotone, and nothing else of the wire can be read.
+// WIRE_ARRAYS: an array its totals call for is missing, or 16-bit indices
+// come with more than 65,536 strings; only the device path minds.
+enum WireFault { WIRE_OK = 0, WIRE_OFFSETS, WIRE_ARRAYS };
+WireFault check_wire(const dp_wire32* w) {
+  const int32_t P = w->n_problems;
+  if (P < 0 || !monotone(w->prob_var_off, P) || !monotone(w->prob_con_off, P) || !monotone(w->prob_arg_off, P))
+    return WIRE_OFFSETS;
+  const int32_t nvars = w->prob_var_off[P] - w->prob_var_off[0], ncons = w->prob_con_off[P] - w->prob_con_off[0],
+                nargs = w->prob_arg_off[P] - w->prob_arg_off[0];
+  const bool ids16 = w->var_id16 != nullptr;
+  if ((nvars > 0 && (!(ids16 ? (const void*)w->var_id16 : (const void*)w->var_id) || !w->var_ncon)) ||
+      (ncons > 0 && (!w->con_kn || !w->con_nargs)) ||
+      (nargs > 0 && !(ids16 ? (const void*)w->con_arg16 : (const void*)w->con_arg)) ||
+      (ids16 && w->n_strs > 65536))
+    return WIRE_ARRAYS;
+  return WIRE_OK;
+}
 }  // namespace
 
 // The packing's stream at the highest priority: a queue of its own, so its
@@ -1108,11 +1272,8 @@ void dp_dlower_free(dp_dlower* d) { delete d; }
 int64_t dp_dlower_host_count(const dp_dlower* d) { return d ? d->host_count : 0; }
 
 int dp_lower_device(dp_dlower* d, const dp_wire32* w, int32_t flags, dp_lowered* lw) {
-  if (!d || !lw || !w || w->n_problems < 0 || !monotone(w->prob_var_off, w->n_problems) ||
-      !monotone(w->prob_con_off, w->n_problems) || !monotone(w->prob_arg_off, w->n_problems)) {
-    dp::set_global_error("dp_lower: malformed wire batch");
-    return -1;
-  }
+  const WireFault fault = d && lw && w ? check_wire(w) : WIRE_OFFSETS;
+  if (fault == WIRE_OFFSETS) return dl_fail("dp_lower: malformed wire batch");
   std::lock_guard<std::mutex> lk(d->mu);
   const double t0 = dl_ms();
   const int32_t P = w->n_problems;
@@ -1120,85 +1281,19 @@ int dp_lower_device(dp_dlower* d, const dp_wire32* w, int32_t flags, dp_lowered*
                     !(flags & DP_LOWER_NO_P8) && dp::ldsg_env() != dp::LDSG_ALWAYS && P > 0;
   if (!ours) return lower_on_host(w, flags, lw, d);
   if (!device_takes(w)) return lower_on_host(w, flags, lw, d);
-  const int32_t pv0 = w->prob_var_off[0], cb0 = w->prob_con_off[0], ab0 = w->prob_arg_off[0];
-  const int32_t nvars = w->prob_var_off[P] - pv0, ncons = w->prob_con_off[P] - cb0, nargs = w->prob_arg_off[P] - ab0;
-  const bool ids16 = w->var_id16 != nullptr;
-  if ((nvars > 0 && (!(ids16 ? (const void*)w->var_id16 : (const void*)w->var_id) || !w->var_ncon)) ||
-      (ncons > 0 && (!w->con_kn || !w->con_nargs)) ||
-      (nargs > 0 && !(ids16 ? (const void*)w->con_arg16 : (const void*)w->con_arg)) ||
-      (ids16 && w->n_strs > 65536)) {
-    dp::set_global_error("dp_lower: malformed wire batch");
-    return -1;
-  }
+  if (fault != WIRE_OK) return dl_fail("dp_lower: malformed wire batch");
+  const int64_t nvars = w->prob_var_off[P] - w->prob_var_off[0], ncons = w->prob_con_off[P] - w->prob_con_off[0],
+                nargs = w->prob_arg_off[P] - w->prob_arg_off[0];
   DL_OK(hipSetDevice(d->dev));
-  DL_OK(d->pvo.need((size_t)P + 1));
-  DL_OK(d->pco.need((size_t)P + 1));
-  DL_OK(d->pao.need((size_t)P + 1));
-  if (ids16) {
-    DL_OK(d->vid16.need((size_t)nvars + 1));
-    DL_OK(d->arg16.need((size_t)nargs + 1));
-  } else {
-    DL_OK(d->vid.need((size_t)nvars + 1));
-    DL_OK(d->arg.need((size_t)nargs + 1));
-  }
-  DL_OK(d->vnc.need((size_t)nvars + 1));
-  DL_OK(d->ckn.need((size_t)ncons + 1));
-  DL_OK(d->cna.need((size_t)ncons + 1));
-  DL_OK(d->words.need((size_t)P));
-  DL_OK(d->nid.need((size_t)P));
-  DL_OK(d->slots.need((size_t)P * DL_SLOT));
-  DL_OK(d->ivs.need((size_t)P * DL_C));
-  DL_OK(d->ics.need((size_t)P * DL_C));
   DL_OK(d->ro.need((size_t)P + 1));
   DL_OK(d->io.need((size_t)P + 1));
-  if (d->h_cap < 2 * ((size_t)P + 1)) {
-    if (d->h_off) dp::pinned_free(d->h_off);
-    d->h_cap = 2 * ((size_t)P + 1) + P / 4;
-    d->h_off = static_cast<int64_t*>(dp::pinned_alloc(d->h_cap * sizeof(int64_t)));
-    if (!d->h_off) {
-      d->h_cap = 0;
-      dp::set_global_error("dp_lower_device: page-locked allocation failed");
-      return -1;
-    }
-  }
-  hipStream_t st = d->st, cst = d->cst;
-  auto h2d = [&](auto* dst, const auto* src, int64_t n) {
-    return n > 0 ? hipMemcpyAsync(dst, src, (size_t)n * sizeof(*src), hipMemcpyHostToDevice, cst) : hipSuccess;
-  };
-  DL_OK(h2d(d->pvo.p, w->prob_var_off, (int64_t)P + 1));
-  DL_OK(h2d(d->pco.p, w->prob_con_off, (int64_t)P + 1));
-  DL_OK(h2d(d->pao.p, w->prob_arg_off, (int64_t)P + 1));
-  DlArgs a{};
-  a.pvo = d->pvo.p;
-  a.pco = d->pco.p;
-  a.pao = d->pao.p;
-  a.vid = d->vid.p;
-  a.vnc = d->vnc.p;
-  a.ckn = d->ckn.p;
-  a.cna = d->cna.p;
-  a.arg = d->arg.p;
-  a.vid16 = d->vid16.p;
-  a.arg16 = d->arg16.p;
-  a.ids16 = ids16 ? 1 : 0;
-  a.pbase = pv0;
-  a.cbase = cb0;
-  a.abase = ab0;
-  a.nvars = nvars;
-  a.ncons = ncons;
-  a.nargs = nargs;
-  a.n_strs = w->n_strs;
-  a.group_above = dp::group_above();
-  a.words = d->words.p;
-  a.nid = d->nid.p;
-  a.slots = d->slots.p;
-  a.ivs = d->ivs.p;
-  a.ics = d->ics.p;
+  if (!d->h_off.need(2 * ((size_t)P + 1))) return dl_fail("dp_lower_device: page-locked allocation failed");
   // Every size bounded from the batch's totals (a record's words: at most
   // 23 + (2 (args + constraints) + 2 variables + 4 constraints) / 4, an
   // identity per constraint), so the result is sized before the kernels run
   // and each piece is packed straight into place.
-  const int64_t bound_words = 24 * (int64_t)P + (2 * ((int64_t)nargs + ncons) + 2 * (int64_t)nvars + 4 * (int64_t)ncons) / 4;
-  const dp::LoweredOut O = dp::lowered_prepare(lw, P, bound_words, (int64_t)ncons + 1, (flags & DP_LOWER_PINNED) != 0);
+  const int64_t bound_words = 24 * (int64_t)P + (2 * (nargs + ncons) + 2 * nvars + 4 * ncons) / 4;
+  const dp::LoweredOut O = dp::lowered_prepare(lw, P, bound_words, ncons + 1, (flags & DP_LOWER_PINNED) != 0);
   // page-locked results are written by the pack kernel through their device
   // mapping; otherwise into device buffers and copied back
   int32_t *trec = nullptr, *tivar = nullptr, *ticon = nullptr;
@@ -1221,60 +1316,40 @@ int dp_lower_device(dp_dlower* d, const dp_wire32* w, int32_t flags, dp_lowered*
     tivar = d->ivar.p;
     ticon = d->icon.p;
   }
-  // pieces: the wire's copy of piece k+1 runs under the lowering and packing
-  // of piece k.  Every copy and its event is enqueued first: an event marker
-  // may share a hardware queue with the packing's stream, and one enqueued
-  // after pack(k) would hold lower(k+1) behind it.
-  const int pieces = (int)std::min<int64_t>(dp_dlower::kMaxPieces, std::max<int64_t>(1, P / 2048));
-  auto piece = [&](int k, int32_t& q0, int32_t& q1) {
-    q0 = (int32_t)((int64_t)P * k / pieces);
-    q1 = (int32_t)((int64_t)P * (k + 1) / pieces);
-  };
-  for (int k = 0; k < pieces; ++k) {
-    int32_t q0, q1;
-    piece(k, q0, q1);
-    const int32_t v0 = w->prob_var_off[q0], v1 = w->prob_var_off[q1];
-    const int32_t c0 = w->prob_con_off[q0], c1 = w->prob_con_off[q1];
-    const int32_t x0 = w->prob_arg_off[q0], x1 = w->prob_arg_off[q1];
-    if (ids16) DL_OK(h2d(d->vid16.p + (v0 - pv0), w->var_id16 + v0, v1 - v0));
-    else DL_OK(h2d(d->vid.p + (v0 - pv0), w->var_id + v0, v1 - v0));
-    DL_OK(h2d(d->vnc.p + (v0 - pv0), w->var_ncon + v0, v1 - v0));
-    DL_OK(h2d(d->ckn.p + (c0 - cb0), w->con_kn + c0, c1 - c0));
-    DL_OK(h2d(d->cna.p + (c0 - cb0), w->con_nargs + c0, c1 - c0));
-    if (ids16) DL_OK(h2d(d->arg16.p + (x0 - ab0), w->con_arg16 + x0, x1 - x0));
-    else DL_OK(h2d(d->arg.p + (x0 - ab0), w->con_arg + x0, x1 - x0));
-    DL_OK(hipEventRecord(d->ev[k], cst));
+  // Behind each piece's lowering its offsets are scanned, and its slots packed
+  // into place on the packing's stream, under the next piece's lowering.
+  WireStage& S = d->fw[0].wire;
+  hipStream_t st = d->st, pst = d->pst;
+  int k = 0;
+  const int64_t copied = S.enqueue(d, w, 0, P, [&](int32_t r0, int32_t r1) {
+    hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(SCAN_T), 0, st, S.words.p, S.nid.p, r0, r1, d->ro.p, d->io.p);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipEventRecord(d->es[k], st);
+    if (e == hipSuccess) e = hipStreamWaitEvent(pst, d->es[k++], 0);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(pack_kernel, dim3((unsigned)(r1 - r0)), dim3(DL_T), 0, pst, r0, S.words.p, S.nid.p, S.slots.p,
+                       S.ivs.p, S.ics.p, d->ro.p, d->io.p, trec, tivar, ticon);
+    return hipGetLastError();
+  });
+  // From the first enqueue on, an error drains the streams before it returns.
+  if (copied < 0) {
+    drain(d);
+    return -1;
   }
-  for (int k = 0; k < pieces; ++k) {
-    int32_t q0, q1;
-    piece(k, q0, q1);
-    DL_OK(hipStreamWaitEvent(st, d->ev[k], 0));
-    if (q1 == q0) continue;
-    a.p0 = q0;
-    hipLaunchKernelGGL(lower_kernel, dim3((unsigned)(q1 - q0)), dim3(DL_T), 0, st, a);
-    DL_OK(hipGetLastError());
-    hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(SCAN_T), 0, st, d->words.p, d->nid.p, q0, q1, d->ro.p, d->io.p);
-    DL_OK(hipGetLastError());
-    DL_OK(hipEventRecord(d->es[k], st));
-    DL_OK(hipStreamWaitEvent(d->pst, d->es[k], 0));
-    hipLaunchKernelGGL(pack_kernel, dim3((unsigned)(q1 - q0)), dim3(DL_T), 0, d->pst, q0, d->words.p, d->nid.p,
-                       d->slots.p, d->ivs.p, d->ics.p, d->ro.p, d->io.p, trec, tivar, ticon);
-    DL_OK(hipGetLastError());
-  }
-  int64_t* h_ro = d->h_off;
-  int64_t* h_io = d->h_off + P + 1;
-  DL_OK(hipMemcpyAsync(h_ro, d->ro.p, ((size_t)P + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-  DL_OK(hipMemcpyAsync(h_io, d->io.p, ((size_t)P + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-  DL_OK(hipStreamSynchronize(st));
+  int64_t* h_ro = d->h_off.p;
+  int64_t* h_io = d->h_off.p + P + 1;
+  DL_OK_DRAIN(hipMemcpyAsync(h_ro, d->ro.p, ((size_t)P + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  DL_OK_DRAIN(hipMemcpyAsync(h_io, d->io.p, ((size_t)P + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  DL_OK_DRAIN(hipStreamSynchronize(st));
   const double t_dev = dl_ms();
   const int64_t rw = h_ro[P], ni = h_io[P];
   std::memcpy(O.rec_off, h_ro, ((size_t)P + 1) * sizeof(int64_t));
   std::memcpy(O.ident_off, h_io, ((size_t)P + 1) * sizeof(int64_t));
   if (!mapped) {  // (after the packs, on their stream)
-    if (rw) DL_OK(hipMemcpyAsync(O.rec, d->rec.p, (size_t)rw * sizeof(int32_t), hipMemcpyDeviceToHost, d->pst));
+    if (rw) DL_OK_DRAIN(hipMemcpyAsync(O.rec, d->rec.p, (size_t)rw * sizeof(int32_t), hipMemcpyDeviceToHost, pst));
     if (ni) {
-      DL_OK(hipMemcpyAsync(O.ivar, d->ivar.p, (size_t)ni * sizeof(int32_t), hipMemcpyDeviceToHost, d->pst));
-      DL_OK(hipMemcpyAsync(O.icon, d->icon.p, (size_t)ni * sizeof(int32_t), hipMemcpyDeviceToHost, d->pst));
+      DL_OK_DRAIN(hipMemcpyAsync(O.ivar, d->ivar.p, (size_t)ni * sizeof(int32_t), hipMemcpyDeviceToHost, pst));
+      DL_OK_DRAIN(hipMemcpyAsync(O.icon, d->icon.p, (size_t)ni * sizeof(int32_t), hipMemcpyDeviceToHost, pst));
     }
   }
   // the problems the kernel left to the host, found while the copies run
@@ -1282,7 +1357,7 @@ int dp_lower_device(dp_dlower* d, const dp_wire32* w, int32_t flags, dp_lowered*
   for (int32_t p = 0; p < P; ++p)
     if (h_ro[p + 1] == h_ro[p]) d->which.push_back(p);
   d->host_count = (int64_t)d->which.size();
-  DL_OK(hipStreamSynchronize(d->pst));
+  DL_OK_DRAIN(hipStreamSynchronize(pst));
   const double t_pack = dl_ms();
   if (d->which.empty()) {
     if (dl_times()) std::fprintf(stderr, "dp_lower_device: P %d device %.3f pack %.3f ms\n", P, t_dev - t0, t_pack - t0);
@@ -1291,10 +1366,8 @@ int dp_lower_device(dp_dlower* d, const dp_wire32* w, int32_t flags, dp_lowered*
   dp_wire sub{};
   host_subwire(d, w, &sub);
   const double t_sub = dl_ms();
-  if (dp::lowered_splice(lw, &sub, flags, d->which.data(), (int32_t)d->which.size()) != 0) {
-    dp::set_global_error("dp_lower: malformed wire batch");
-    return -1;
-  }
+  if (dp::lowered_splice(lw, &sub, flags, d->which.data(), (int32_t)d->which.size()) != 0)
+    return dl_fail("dp_lower: malformed wire batch");
   if (dl_times())
     std::fprintf(stderr, "dp_lower_device: P %d device %.3f pack %.3f sub-wire %.3f splice %.3f ms (%d on the host)\n", P,
                  t_dev - t0, t_pack - t0, t_sub - t_pack, dl_ms() - t_sub, (int)d->which.size());
@@ -1308,105 +1381,29 @@ int dp_lower_device(dp_dlower* d, const dp_wire32* w, int32_t flags, dp_lowered*
 // ---------------------------------------------------------------------------
 namespace {
 
-struct FusedTimes {
-  double lower_wait = 0, plan = 0, host = 0, wait = 0, merge = 0;
+// One call's accounting and its job beside the windows'.
+struct FusedCall {
+  int64_t h2d = 0, d2h = 0;  // this thread's copies, then each waited job's
+  dp_job* side_job = nullptr;  // the host-lowered problems' job
+  int64_t side_h2d = 0, side_d2h = 0;  // (its own counters: jobs run side by side)
+  double lower_wait = 0, plan = 0, host = 0, wait = 0;  // ms
 };
 
 // Enqueue the wire copy, the lowering and the header kernel of window
-// [q0, q1) into B (the window as a batch of its own: offsets from its first
-// element), recording B.lowered behind them.  Returns the bytes copied to the
-// device, or -1.
+// [q0, q1) into B, recording B.lowered behind them.  Returns the bytes copied
+// to the device, or -1.
 int64_t enqueue_window(dp_dlower* d, FusedWin& B, const dp_wire32* w, int32_t q0, int32_t q1) {
   const int32_t n = q1 - q0;
-  const int32_t pv0 = w->prob_var_off[q0], cb0 = w->prob_con_off[q0], ab0 = w->prob_arg_off[q0];
-  const int32_t nvars = w->prob_var_off[q1] - pv0, ncons = w->prob_con_off[q1] - cb0,
-                nargs = w->prob_arg_off[q1] - ab0;
-  const bool ids16 = w->var_id16 != nullptr;
   B.q0 = q0;
   B.n = n;
-  DL_OK(B.pvo.need((size_t)n + 1));
-  DL_OK(B.pco.need((size_t)n + 1));
-  DL_OK(B.pao.need((size_t)n + 1));
-  if (ids16) {
-    DL_OK(B.vid16.need((size_t)nvars + 1));
-    DL_OK(B.arg16.need((size_t)nargs + 1));
-  } else {
-    DL_OK(B.vid.need((size_t)nvars + 1));
-    DL_OK(B.arg.need((size_t)nargs + 1));
-  }
-  DL_OK(B.vnc.need((size_t)nvars + 1));
-  DL_OK(B.ckn.need((size_t)ncons + 1));
-  DL_OK(B.cna.need((size_t)ncons + 1));
-  DL_OK(B.words.need((size_t)n));
-  DL_OK(B.nid.need((size_t)n));
-  DL_OK(B.slots.need((size_t)n * DL_SLOT));
-  DL_OK(B.ivs.need((size_t)n * DL_C));
-  DL_OK(B.ics.need((size_t)n * DL_C));
   DL_OK(B.heads.need((size_t)n * DP_H_SIZE));
   DL_OK(B.counts.need((size_t)n * 2));
-  hipStream_t st = d->st, cst = d->cst;
-  int64_t bytes = 0;
-  auto h2d = [&](auto* dst, const auto* src, int64_t m) {
-    bytes += m > 0 ? m * (int64_t)sizeof(*src) : 0;
-    return m > 0 ? hipMemcpyAsync(dst, src, (size_t)m * sizeof(*src), hipMemcpyHostToDevice, cst) : hipSuccess;
-  };
-  DL_OK(h2d(B.pvo.p, w->prob_var_off + q0, (int64_t)n + 1));
-  DL_OK(h2d(B.pco.p, w->prob_con_off + q0, (int64_t)n + 1));
-  DL_OK(h2d(B.pao.p, w->prob_arg_off + q0, (int64_t)n + 1));
-  DlArgs a{};
-  a.pvo = B.pvo.p;
-  a.pco = B.pco.p;
-  a.pao = B.pao.p;
-  a.vid = B.vid.p;
-  a.vnc = B.vnc.p;
-  a.ckn = B.ckn.p;
-  a.cna = B.cna.p;
-  a.arg = B.arg.p;
-  a.vid16 = B.vid16.p;
-  a.arg16 = B.arg16.p;
-  a.ids16 = ids16 ? 1 : 0;
-  a.pbase = pv0;
-  a.cbase = cb0;
-  a.abase = ab0;
-  a.nvars = nvars;
-  a.ncons = ncons;
-  a.nargs = nargs;
-  a.n_strs = w->n_strs;
-  a.group_above = dp::group_above();
-  a.words = B.words.p;
-  a.nid = B.nid.p;
-  a.slots = B.slots.p;
-  a.ivs = B.ivs.p;
-  a.ics = B.ics.p;
-  // pieces, as dp_lower_device: piece k+1's copy runs under piece k's lowering
-  const int pieces = (int)std::min<int64_t>(dp_dlower::kMaxPieces, std::max<int64_t>(1, n / 2048));
-  auto piece = [&](int k) { return q0 + (int32_t)((int64_t)n * k / pieces); };
-  for (int k = 0; k < pieces; ++k) {
-    const int32_t r0 = piece(k), r1 = piece(k + 1);
-    const int32_t v0 = w->prob_var_off[r0], v1 = w->prob_var_off[r1];
-    const int32_t c0 = w->prob_con_off[r0], c1 = w->prob_con_off[r1];
-    const int32_t x0 = w->prob_arg_off[r0], x1 = w->prob_arg_off[r1];
-    if (ids16) DL_OK(h2d(B.vid16.p + (v0 - pv0), w->var_id16 + v0, v1 - v0));
-    else DL_OK(h2d(B.vid.p + (v0 - pv0), w->var_id + v0, v1 - v0));
-    DL_OK(h2d(B.vnc.p + (v0 - pv0), w->var_ncon + v0, v1 - v0));
-    DL_OK(h2d(B.ckn.p + (c0 - cb0), w->con_kn + c0, c1 - c0));
-    DL_OK(h2d(B.cna.p + (c0 - cb0), w->con_nargs + c0, c1 - c0));
-    if (ids16) DL_OK(h2d(B.arg16.p + (x0 - ab0), w->con_arg16 + x0, x1 - x0));
-    else DL_OK(h2d(B.arg.p + (x0 - ab0), w->con_arg + x0, x1 - x0));
-    DL_OK(hipEventRecord(d->ev[k], cst));
-  }
-  for (int k = 0; k < pieces; ++k) {
-    const int32_t r0 = piece(k), r1 = piece(k + 1);
-    DL_OK(hipStreamWaitEvent(st, d->ev[k], 0));
-    if (r1 == r0) continue;
-    a.p0 = r0 - q0;
-    hipLaunchKernelGGL(lower_kernel, dim3((unsigned)(r1 - r0)), dim3(DL_T), 0, st, a);
-    DL_OK(hipGetLastError());
-  }
+  const int64_t bytes = B.wire.enqueue(d, w, q0, q1, [](int32_t, int32_t) { return hipSuccess; });
+  if (bytes < 0) return -1;
   hipLaunchKernelGGL(heads_kernel, dim3((unsigned)(((int64_t)n * DP_H_SIZE + HEADS_T - 1) / HEADS_T)), dim3(HEADS_T),
-                     0, st, n, B.words.p, B.nid.p, B.slots.p, B.heads.d, B.counts.d);
+                     0, d->st, n, B.wire.words.p, B.wire.nid.p, B.wire.slots.p, B.heads.d, B.counts.d);
   DL_OK(hipGetLastError());
-  DL_OK(hipEventRecord(B.lowered, st));
+  DL_OK(hipEventRecord(B.lowered, d->st));
   return bytes;
 }
 
@@ -1416,325 +1413,294 @@ int32_t fused_window() {  // (read per call)
   return v > 0 ? (int32_t)std::min<long long>(v, kFusedWindow) : kFusedWindow;
 }
 
+// Wait for B's job, if it has one, and take its PCIe bytes.
+int wait_window(dp_dlower* d, FusedWin& B, FusedCall& c) {
+  if (!B.job) return 0;
+  const int rc = dp_job_wait(d->ctx, B.job);
+  B.job = nullptr;
+  c.h2d += B.job_h2d;
+  c.d2h += B.job_d2h;
+  return rc ? -1 : 0;
+}
+
+// Every job still in flight is waited for: the windows', then the
+// host-lowered problems'.
+int settle(dp_dlower* d, FusedCall& c) {
+  int rc = 0;
+  for (auto& B : d->fw)
+    if (wait_window(d, B, c)) rc = -1;
+  if (c.side_job) {
+    if (dp_job_wait(d->ctx, c.side_job)) rc = -1;
+    c.side_job = nullptr;
+    c.h2d += c.side_h2d;
+    c.d2h += c.side_d2h;
+  }
+  return rc;
+}
+
+// The error exit of a call that has begun (the step that failed has set the
+// text): nothing is left running, and what the call wrote is forgotten.
+int fail(dp_dlower* d, FusedCall& c) {
+  const std::string keep = dp_last_global_error();
+  drain(d);
+  (void)settle(d, c);
+  d->v.core.wipe();
+  d->s.core.wipe();
+  d->m.core.wipe();
+  dp::set_global_error(keep);
+  return -1;
+}
+
+// Window B is lowered: its result layout from its headers (a problem without
+// a record takes no room and goes to the host, d->which), then the job that
+// solves it from the slots where they lie.
+int submit_window(dp_dlower* d, FusedWin& B, int64_t inst_cap, int64_t core_cap) {
+  ResultStage& V = d->v;
+  int64_t* io = V.inst_off.p + B.q0;
+  int64_t* co = V.core_off.p + B.q0;
+  for (int32_t i = 0; i < B.n; ++i) {
+    const int32_t words = B.counts.h[2 * (size_t)i];
+    const int32_t* h = B.heads.h + (size_t)i * DP_H_SIZE;
+    if (words <= 0) d->which.push_back(B.q0 + i);
+    io[i + 1] = io[i] + (words > 0 ? dp::bits_words(h[DP_H_NV]) : 0);
+    co[i + 1] = co[i] + (words > 0 ? std::max(0, B.counts.h[2 * (size_t)i + 1]) : 0);
+  }
+  if (io[B.n] > inst_cap || co[B.n] > core_cap) return dl_fail("dp_lower_solve: inconsistent record headers");
+  dp::FusedSrc F{};
+  F.heads = B.heads.h;
+  F.rec_off = d->f_rec_off.data();
+  F.dev_rec = B.wire.slots.p;
+  F.dev_nid = B.wire.nid.p;
+  F.dev_ivs = B.wire.ivs.p;
+  F.dev_ics = B.wire.ics.p;
+  F.owner_stride = DL_C;
+  F.core_var = V.core.cvar.p;
+  F.core_con = V.core.ccon.p;
+  dp_batch fb{B.n, d->f_rec_off.data(), nullptr};
+  dp_result fr = V.at(B.q0);
+  B.job_h2d = B.job_d2h = 0;
+  if (dp::submit_job(d->ctx, &fb, &fr, &F, &B.job_h2d, &B.job_d2h, &B.job) != 0)
+    return dl_fail("dp_lower_solve: the solve could not be submitted");
+  return 0;
+}
+
+// The fused windows: at most `win` problems' slots and owners live at once.
+// A batch of several windows alternates two buffers of half a window each, so
+// window k+1 is copied and lowered under window k's solve.  Their jobs are
+// left in flight.
+int run_windows(dp_dlower* d, const dp_wire32* w, FusedCall& c) {
+  if (hipSetDevice(d->dev) != hipSuccess) return dl_fail("dp_lower_solve: hipSetDevice failed");
+  const int32_t P = w->n_problems;
+  const int32_t W = fused_window();
+  const int32_t win = P <= W ? P : std::max<int32_t>(1, W / 2);
+  const int32_t nwin = (P + win - 1) / win;
+  // staging of the windows' results, sized from the wire's totals (a bitmap
+  // word per 32 variables, an identity per constraint at most)
+  const int64_t core_cap = w->prob_con_off[P] - w->prob_con_off[0];
+  int64_t inst_cap = 0;
+  for (int32_t p = 0; p < P; ++p) inst_cap += dp::bits_words(w->prob_var_off[p + 1] - w->prob_var_off[p]);
+  if (!d->v.need_data((size_t)inst_cap, (size_t)core_cap))
+    return dl_fail("dp_lower_solve: page-locked allocation failed");
+  if (d->f_rec_off.size() < (size_t)win + 1) {
+    d->f_rec_off.resize((size_t)win + 1);
+    for (int32_t i = 0; i <= win; ++i) d->f_rec_off[(size_t)i] = (int64_t)i * DL_SLOT;
+  }
+  auto enqueue = [&](int k) {
+    const int32_t q0 = k * win, q1 = (int32_t)std::min<int64_t>(P, (int64_t)q0 + win);
+    const int64_t b = enqueue_window(d, d->fw[k & 1], w, q0, q1);
+    if (b > 0) c.h2d += b;
+    return b < 0 ? -1 : 0;
+  };
+  if (enqueue(0)) return -1;
+  for (int k = 0; k < nwin; ++k) {
+    FusedWin& B = d->fw[k & 1];
+    const double ta = dl_ms();
+    if (hipEventSynchronize(B.lowered) != hipSuccess) return dl_fail("dp_lower_solve: the lowering failed on the device");
+    const double tb = dl_ms();
+    c.lower_wait += tb - ta;
+    c.d2h += (int64_t)B.n * (DP_H_SIZE + 2) * 4;
+    if (submit_window(d, B, inst_cap, core_cap)) return -1;
+    c.plan += dl_ms() - tb;
+    if (k + 1 == nwin) break;
+    // window k-1: its solve reads the slots window k+1 is lowered into
+    const double tw = dl_ms();
+    const int rc = wait_window(d, d->fw[(k + 1) & 1], c);
+    c.wait += dl_ms() - tw;
+    if (rc) return dl_fail(dp_last_error(d->ctx));
+    if (enqueue(k + 1)) return -1;
+  }
+  return 0;
+}
+
+// The problems d->which, left to the host: lowered there while the fused
+// windows solve, then submitted as an ordinary job beside them.
+int submit_host_side(dp_dlower* d, const dp_wire32* w, FusedCall& c) {
+  const int32_t nw = (int32_t)d->which.size();
+  ResultStage& S = d->s;
+  dp_wire sub{};
+  host_subwire(d, w, &sub);
+  if (!d->side) d->side = dp_lowered_new();
+  if (dp_lower_into(&sub, DP_LOWER_NARROW | DP_LOWER_PACKED | DP_LOWER_PINNED, d->side) != 0)
+    return dl_fail("dp_lower: malformed wire batch");
+  dp_batch sb{nw, dp_lowered_rec_off(d->side), dp_lowered_rec(d->side)};
+  if (!S.need((size_t)nw) || dp_result_layout(&sb, S.inst_off.p, S.core_off.p) != 0 ||
+      !S.need_data((size_t)S.inst_off.p[nw], (size_t)S.core_off.p[nw]))
+    return dl_fail("dp_lower_solve: page-locked allocation failed");
+  d->f_err.assign((size_t)nw, 0);
+  (void)dp_lowered_errors(d->side, d->f_err.data());
+  dp_result sr = S.at(0);
+  if (dp::submit_job(d->ctx, &sb, &sr, nullptr, &c.side_h2d, &c.side_d2h, &c.side_job) != 0)
+    return dl_fail("dp_lower_solve: the solve could not be submitted");
+  return 0;
+}
+
+// The host-lowered problems' owners (identity -> AppliedConstraint, on the
+// host), and their per-problem rows into the call's.
+void map_host_side(dp_dlower* d) {
+  const int32_t nw = (int32_t)d->which.size();
+  ResultStage &S = d->s, &V = d->v;
+  const int64_t* io = dp_lowered_ident_off(d->side);
+  const int32_t* iv = dp_lowered_ident_var(d->side);
+  const int32_t* ic = dp_lowered_ident_con(d->side);
+  for (int32_t j = 0; j < nw; ++j) {
+    const int32_t len = S.core_len.p[j];
+    if (len <= 0) continue;
+    const int64_t at = S.core_off.p[j], nid = io[j + 1] - io[j];
+    for (int32_t k = 0; k < len; ++k) {
+      const int32_t id = S.core.core.p[at + k];
+      const bool ok = id >= 0 && id < nid;
+      S.core.cvar.p[at + k] = ok ? iv[io[j] + id] : -1;
+      S.core.ccon.p[at + k] = ok ? ic[io[j] + id] : -1;
+    }
+    S.core.dirty.emplace_back(at, len);
+  }
+  for (int32_t j = 0; j < nw; ++j) {
+    const int32_t p = d->which[(size_t)j];
+    d->o_err.p[p] = d->f_err[(size_t)j];
+    V.status.p[p] = S.status.p[j];
+    V.flags.p[p] = S.flags.p[j];
+    V.steps.p[p] = S.steps.p[j];
+    V.core_len.p[p] = S.core_len.p[j];
+  }
+}
+
+// The windows' layout and the host side's merged by problem index into d->m.
+int merge_by_problem(dp_dlower* d, int32_t P) {
+  const int32_t nw = (int32_t)d->which.size();
+  ResultStage &V = d->v, &S = d->s, &M = d->m;
+  if (!M.need((size_t)P, false)) return dl_fail("dp_lower_solve: page-locked allocation failed");
+  int64_t* mi = M.inst_off.p;
+  int64_t* mc = M.core_off.p;
+  mi[0] = mc[0] = 0;
+  for (int32_t p = 0, j = 0; p < P; ++p) {
+    const bool host = j < nw && d->which[(size_t)j] == p;
+    mi[p + 1] = mi[p] + (host ? S.inst_off.p[j + 1] - S.inst_off.p[j] : V.inst_off.p[p + 1] - V.inst_off.p[p]);
+    mc[p + 1] = mc[p] + (host ? S.core_off.p[j + 1] - S.core_off.p[j] : V.core_off.p[p + 1] - V.core_off.p[p]);
+    j += host;
+  }
+  if (!M.need_data((size_t)mi[P], (size_t)mc[P])) return dl_fail("dp_lower_solve: page-locked allocation failed");
+  for (int32_t p = 0, j = 0; p < P; ++p) {
+    const bool host = j < nw && d->which[(size_t)j] == p;
+    const uint32_t* si = host ? S.inst.p + S.inst_off.p[j] : V.inst.p + V.inst_off.p[p];
+    std::memcpy(M.inst.p + mi[p], si, (size_t)(mi[p + 1] - mi[p]) * 4);
+    const int32_t len = (int32_t)std::min<int64_t>(V.core_len.p[p], mc[p + 1] - mc[p]);
+    if (len > 0) {
+      const CoreSet& C = host ? S.core : V.core;
+      const int64_t at = host ? S.core_off.p[j] : V.core_off.p[p];
+      std::memcpy(M.core.core.p + mc[p], C.core.p + at, (size_t)len * 4);
+      std::memcpy(M.core.cvar.p + mc[p], C.cvar.p + at, (size_t)len * 4);
+      std::memcpy(M.core.ccon.p + mc[p], C.ccon.p + at, (size_t)len * 4);
+      M.core.dirty.emplace_back(mc[p], len);
+    }
+    j += host;
+  }
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
 
 int dp_lower_solve(dp_dlower* d, const dp_wire32* w, dp_solved* out) {
-  if (!d || !w || !out) {
-    dp::set_global_error("dp_lower_solve: null argument");
-    return -1;
-  }
-  if (w->n_problems < 0 || !monotone(w->prob_var_off, w->n_problems) || !monotone(w->prob_con_off, w->n_problems) ||
-      !monotone(w->prob_arg_off, w->n_problems)) {
-    dp::set_global_error("dp_lower: malformed wire batch");
-    return -1;
-  }
+  if (!d || !w || !out) return dl_fail("dp_lower_solve: null argument");
+  const WireFault fault = check_wire(w);
+  if (fault == WIRE_OFFSETS) return dl_fail("dp_lower: malformed wire batch");
   std::lock_guard<std::mutex> lk(d->mu);
   const double t0 = dl_ms();
-  FusedTimes tm;
+  FusedCall c;
   const int32_t P = w->n_problems;
+  ResultStage& V = d->v;
   *out = dp_solved{};
   d->f_which.clear();
   d->f_err.clear();
   d->host_count = 0;
-  d->v_core.clean();
-  d->s_core.clean();
-  d->m_core.clean();
-  if (!d->o_err.need((size_t)P + 1) || !d->o_flags.need((size_t)P + 1) || !d->o_core_len.need((size_t)P + 1) ||
-      !d->o_status.need((size_t)P + 1) || !d->o_steps.need((size_t)P + 1) || !d->v_inst_off.need((size_t)P + 1) ||
-      !d->v_core_off.need((size_t)P + 1)) {
-    dp::set_global_error("dp_lower_solve: page-locked allocation failed");
-    return -1;
-  }
+  V.core.clean();
+  d->s.core.clean();
+  d->m.core.clean();
+  if (!d->o_err.need((size_t)P + 1) || !V.need((size_t)P))
+    return dl_fail("dp_lower_solve: page-locked allocation failed");
   std::memset(d->o_err.p, 0, ((size_t)P + 1) * sizeof(int32_t));
-  d->v_inst_off.p[0] = d->v_core_off.p[0] = 0;
+  V.inst_off.p[0] = V.core_off.p[0] = 0;
   out->n_problems = P;
   out->err = d->o_err.p;
-  out->status = d->o_status.p;
-  out->flags = d->o_flags.p;
-  out->steps = d->o_steps.p;
-  out->core_len = d->o_core_len.p;
-  out->inst_off = d->v_inst_off.p;
-  out->core_off = d->v_core_off.p;
+  out->status = V.status.p;
+  out->flags = V.flags.p;
+  out->steps = V.steps.p;
+  out->core_len = V.core_len.p;
   if (P == 0) {
-    if (!d->v_inst.need(1) || !d->v_core.need(1)) {
-      dp::set_global_error("dp_lower_solve: page-locked allocation failed");
-      return -1;
-    }
-    out->installed = d->v_inst.p;
-    out->core = d->v_core.core.p;
-    out->core_var = d->v_core.cvar.p;
-    out->core_con = d->v_core.ccon.p;
+    if (!V.need_data(0, 0)) return dl_fail("dp_lower_solve: page-locked allocation failed");
+    V.publish(out);
     return 0;
   }
-  const int32_t pv0 = w->prob_var_off[0], cb0 = w->prob_con_off[0], ab0 = w->prob_arg_off[0];
-  const int32_t nvars = w->prob_var_off[P] - pv0, ncons = w->prob_con_off[P] - cb0, nargs = w->prob_arg_off[P] - ab0;
-  const bool ids16 = w->var_id16 != nullptr;
-  if ((nvars > 0 && (!(ids16 ? (const void*)w->var_id16 : (const void*)w->var_id) || !w->var_ncon)) ||
-      (ncons > 0 && (!w->con_kn || !w->con_nargs)) ||
-      (nargs > 0 && !(ids16 ? (const void*)w->con_arg16 : (const void*)w->con_arg)) ||
-      (ids16 && w->n_strs > 65536)) {
-    dp::set_global_error("dp_lower: malformed wire batch");
-    return -1;
-  }
+  if (fault != WIRE_OK) return dl_fail("dp_lower: malformed wire batch");
   // The device path, unless the records would not be the forms the solve
   // reads as they lie: placement overrides stage other forms on the host.
   const int32_t forced = DP_OPT_FORCE_GROUP | DP_OPT_FORCE_HBM | DP_OPT_FORCE_MID | DP_OPT_FORCE_LDSG;
   const bool on_device = !(dp::ctx_flags(d->ctx) & forced) && dp::ldsg_env() != dp::LDSG_ALWAYS && device_takes(w);
-  std::vector<int32_t>& which = d->which;
+  std::vector<int32_t>& which = d->which;  // the problems left to the host
   which.clear();
-  int64_t h2d = 0, d2h = 0;  // this thread's copies, then each waited job's
-  int64_t sh2d = 0, sd2h = 0;  // the host-lowered problems' job
-  bool enqueued = false;
-  // Every job still in flight is waited for, and (after the first enqueue)
-  // the lowering's streams are synchronised, before an error returns.
-  auto settle = [&]() {
-    int rc = 0;
-    for (auto& B : d->fw)
-      if (B.job) {
-        if (dp_job_wait(d->ctx, B.job)) rc = -1;
-        B.job = nullptr;
-        h2d += B.job_h2d;
-        d2h += B.job_d2h;
-      }
-    return rc;
-  };
-  auto fail = [&](const char* text) {
-    const std::string keep = text ? std::string(text) : std::string(dp_last_global_error());
-    if (enqueued) {
-      (void)hipStreamSynchronize(d->cst);
-      (void)hipStreamSynchronize(d->st);
-    }
-    (void)settle();
-    d->v_core.wipe();
-    d->s_core.wipe();
-    d->m_core.wipe();
-    dp::set_global_error(keep);
-    return -1;
-  };
   if (on_device) {
-    if (hipSetDevice(d->dev) != hipSuccess) return fail("dp_lower_solve: hipSetDevice failed");
-    // Windows: at most `win` problems' slots and owners live at once.  A
-    // batch of several windows alternates two buffers of half a window each,
-    // so window k+1 is copied and lowered under window k's solve.
-    const int32_t W = fused_window();
-    const int32_t win = P <= W ? P : std::max<int32_t>(1, W / 2);
-    const int32_t nwin = (P + win - 1) / win;
-    // staging of the fused windows' results, sized from the wire's totals (a
-    // bitmap word per 32 variables, an identity per constraint at most)
-    int64_t inst_cap = 0;
-    for (int32_t p = 0; p < P; ++p) inst_cap += dp::bits_words(w->prob_var_off[p + 1] - w->prob_var_off[p]);
-    if (!d->v_inst.need((size_t)inst_cap + 1) || !d->v_core.need((size_t)ncons + 1))
-      return fail("dp_lower_solve: page-locked allocation failed");
-    if (d->f_rec_off.size() < (size_t)win + 1) {
-      d->f_rec_off.resize((size_t)win + 1);
-      for (int32_t i = 0; i <= win; ++i) d->f_rec_off[(size_t)i] = (int64_t)i * DL_SLOT;
-    }
-    auto range = [&](int k, int32_t& q0, int32_t& q1) {
-      q0 = k * win;
-      q1 = std::min<int64_t>(P, (int64_t)q0 + win);
-    };
-    int32_t q0, q1;
-    range(0, q0, q1);
-    enqueued = true;
-    int64_t b = enqueue_window(d, d->fw[0], w, q0, q1);
-    if (b < 0) return fail(nullptr);
-    h2d += b;
-    for (int k = 0; k < nwin; ++k) {
-      FusedWin& B = d->fw[k & 1];
-      const double ta = dl_ms();
-      if (hipEventSynchronize(B.lowered) != hipSuccess) return fail("dp_lower_solve: the lowering failed on the device");
-      const double tb = dl_ms();
-      tm.lower_wait += tb - ta;
-      d2h += (int64_t)B.n * (DP_H_SIZE + 2) * 4;
-      // the window's result layout from its headers; problems without a
-      // record go to the host
-      int64_t* io = d->v_inst_off.p + B.q0;
-      int64_t* co = d->v_core_off.p + B.q0;
-      for (int32_t i = 0; i < B.n; ++i) {
-        const int32_t words = B.counts.h[2 * (size_t)i];
-        const int32_t* h = B.heads.h + (size_t)i * DP_H_SIZE;
-        if (words <= 0) which.push_back(B.q0 + i);
-        io[i + 1] = io[i] + (words > 0 ? dp::bits_words(h[DP_H_NV]) : 0);
-        co[i + 1] = co[i] + (words > 0 ? std::max(0, B.counts.h[2 * (size_t)i + 1]) : 0);
-      }
-      if (io[B.n] > inst_cap || co[B.n] > (int64_t)ncons) return fail("dp_lower_solve: inconsistent record headers");
-      dp::FusedSrc F{};
-      F.heads = B.heads.h;
-      F.rec_off = d->f_rec_off.data();
-      F.dev_rec = B.slots.p;
-      F.dev_nid = B.nid.p;
-      F.dev_ivs = B.ivs.p;
-      F.dev_ics = B.ics.p;
-      F.owner_stride = DL_C;
-      F.core_var = d->v_core.cvar.p;
-      F.core_con = d->v_core.ccon.p;
-      dp_batch fb{B.n, d->f_rec_off.data(), nullptr};
-      dp_result fr{};
-      fr.status = d->o_status.p + B.q0;
-      fr.flags = d->o_flags.p + B.q0;
-      fr.steps = d->o_steps.p + B.q0;
-      fr.core_len = d->o_core_len.p + B.q0;
-      fr.installed = d->v_inst.p;
-      fr.inst_off = io;
-      fr.core = d->v_core.core.p;
-      fr.core_off = co;
-      B.job_h2d = B.job_d2h = 0;
-      if (dp::submit_job(d->ctx, &fb, &fr, &F, &B.job_h2d, &B.job_d2h, &B.job) != 0)
-        return fail("dp_lower_solve: the solve could not be submitted");
-      tm.plan += dl_ms() - tb;
-      if (k + 1 < nwin) {
-        FusedWin& N = d->fw[(k + 1) & 1];
-        if (N.job) {  // window k-1: its solve reads the slots window k+1 is lowered into
-          const double tw = dl_ms();
-          const int rc = dp_job_wait(d->ctx, N.job);
-          N.job = nullptr;
-          h2d += N.job_h2d;
-          d2h += N.job_d2h;
-          tm.wait += dl_ms() - tw;
-          if (rc) return fail(dp_last_error(d->ctx));
-        }
-        range(k + 1, q0, q1);
-        b = enqueue_window(d, N, w, q0, q1);
-        if (b < 0) return fail(nullptr);
-        h2d += b;
-      }
-    }
+    if (run_windows(d, w, c)) return fail(d, c);
   } else {
     which.resize((size_t)P);
     for (int32_t p = 0; p < P; ++p) which[(size_t)p] = p;
   }
-  // The problems left to the host: lowered there while the fused windows
-  // solve, then solved as an ordinary job beside them.
   const int32_t nw = (int32_t)which.size();
-  dp_job* sjob = nullptr;
   const double th = dl_ms();
-  if (nw > 0) {
-    dp_wire sub{};
-    host_subwire(d, w, &sub);
-    if (!d->side) d->side = dp_lowered_new();
-    if (dp_lower_into(&sub, DP_LOWER_NARROW | DP_LOWER_PACKED | DP_LOWER_PINNED, d->side) != 0)
-      return fail("dp_lower: malformed wire batch");
-    dp_batch sb{nw, dp_lowered_rec_off(d->side), dp_lowered_rec(d->side)};
-    if (!d->s_inst_off.need((size_t)nw + 1) || !d->s_core_off.need((size_t)nw + 1) ||
-        dp_result_layout(&sb, d->s_inst_off.p, d->s_core_off.p) != 0 ||
-        !d->s_inst.need((size_t)d->s_inst_off.p[nw] + 1) || !d->s_core.need((size_t)d->s_core_off.p[nw] + 1) ||
-        !d->s_flags.need((size_t)nw) || !d->s_core_len.need((size_t)nw) || !d->s_status.need((size_t)nw) ||
-        !d->s_steps.need((size_t)nw))
-      return fail("dp_lower_solve: page-locked allocation failed");
-    d->f_err.assign((size_t)nw, 0);
-    (void)dp_lowered_errors(d->side, d->f_err.data());
-    dp_result sr{};
-    sr.status = d->s_status.p;
-    sr.flags = d->s_flags.p;
-    sr.steps = d->s_steps.p;
-    sr.core_len = d->s_core_len.p;
-    sr.installed = d->s_inst.p;
-    sr.inst_off = d->s_inst_off.p;
-    sr.core = d->s_core.core.p;
-    sr.core_off = d->s_core_off.p;
-    if (dp::submit_job(d->ctx, &sb, &sr, nullptr, &sh2d, &sd2h, &sjob) != 0)
-      return fail("dp_lower_solve: the solve could not be submitted");
-  }
+  if (nw > 0 && submit_host_side(d, w, c)) return fail(d, c);
   const double tw = dl_ms();
-  tm.host = tw - th;
-  int rc = settle();
-  if (sjob && dp_job_wait(d->ctx, sjob)) rc = -1;
-  if (rc) return fail(dp_last_error(d->ctx));
+  c.host = tw - th;
+  if (settle(d, c)) {
+    dp::set_global_error(dp_last_error(d->ctx));
+    return fail(d, c);
+  }
   const double tmg = dl_ms();
-  tm.wait += tmg - tw;
+  c.wait += tmg - tw;
   // the reported cores of the fused windows (their ranges are zeroed again by the next call)
   if (on_device)
     for (int32_t p = 0; p < P; ++p)
-      if (d->o_core_len.p[p] > 0 && d->v_core_off.p[p + 1] > d->v_core_off.p[p])
-        d->v_core.dirty.emplace_back(d->v_core_off.p[p], d->o_core_len.p[p]);
-  if (nw == 0) {
-    out->installed = d->v_inst.p;
-    out->core = d->v_core.core.p;
-    out->core_var = d->v_core.cvar.p;
-    out->core_con = d->v_core.ccon.p;
-  } else {
-    // the host-lowered problems' owners: identity -> AppliedConstraint on the host
-    const int64_t* io = dp_lowered_ident_off(d->side);
-    const int32_t* iv = dp_lowered_ident_var(d->side);
-    const int32_t* ic = dp_lowered_ident_con(d->side);
-    for (int32_t j = 0; j < nw; ++j) {
-      const int32_t len = d->s_core_len.p[j];
-      if (len <= 0) continue;
-      const int64_t at = d->s_core_off.p[j], nid = io[j + 1] - io[j];
-      for (int32_t k = 0; k < len; ++k) {
-        const int32_t id = d->s_core.core.p[at + k];
-        const bool ok = id >= 0 && id < nid;
-        d->s_core.cvar.p[at + k] = ok ? iv[io[j] + id] : -1;
-        d->s_core.ccon.p[at + k] = ok ? ic[io[j] + id] : -1;
-      }
-      d->s_core.dirty.emplace_back(at, len);
-    }
-    for (int32_t j = 0; j < nw; ++j) {
-      const int32_t p = which[(size_t)j];
-      d->o_err.p[p] = d->f_err[(size_t)j];
-      d->o_status.p[p] = d->s_status.p[j];
-      d->o_flags.p[p] = d->s_flags.p[j];
-      d->o_steps.p[p] = d->s_steps.p[j];
-      d->o_core_len.p[p] = d->s_core_len.p[j];
-    }
-    if (nw == P) {  // all on the host: its layout is the result's
-      out->inst_off = d->s_inst_off.p;
-      out->core_off = d->s_core_off.p;
-      out->installed = d->s_inst.p;
-      out->core = d->s_core.core.p;
-      out->core_var = d->s_core.cvar.p;
-      out->core_con = d->s_core.ccon.p;
-    } else {  // merged by problem index
-      if (!d->m_inst_off.need((size_t)P + 1) || !d->m_core_off.need((size_t)P + 1))
-        return fail("dp_lower_solve: page-locked allocation failed");
-      int64_t* mi = d->m_inst_off.p;
-      int64_t* mc = d->m_core_off.p;
-      mi[0] = mc[0] = 0;
-      for (int32_t p = 0, j = 0; p < P; ++p) {
-        const bool host = j < nw && which[(size_t)j] == p;
-        mi[p + 1] = mi[p] + (host ? d->s_inst_off.p[j + 1] - d->s_inst_off.p[j]
-                                  : d->v_inst_off.p[p + 1] - d->v_inst_off.p[p]);
-        mc[p + 1] = mc[p] + (host ? d->s_core_off.p[j + 1] - d->s_core_off.p[j]
-                                  : d->v_core_off.p[p + 1] - d->v_core_off.p[p]);
-        j += host;
-      }
-      if (!d->m_inst.need((size_t)mi[P] + 1) || !d->m_core.need((size_t)mc[P] + 1))
-        return fail("dp_lower_solve: page-locked allocation failed");
-      for (int32_t p = 0, j = 0; p < P; ++p) {
-        const bool host = j < nw && which[(size_t)j] == p;
-        const uint32_t* si = host ? d->s_inst.p + d->s_inst_off.p[j] : d->v_inst.p + d->v_inst_off.p[p];
-        std::memcpy(d->m_inst.p + mi[p], si, (size_t)(mi[p + 1] - mi[p]) * 4);
-        const int32_t len = (int32_t)std::min<int64_t>(d->o_core_len.p[p], mc[p + 1] - mc[p]);
-        if (len > 0) {
-          const CoreSet& S = host ? d->s_core : d->v_core;
-          const int64_t at = host ? d->s_core_off.p[j] : d->v_core_off.p[p];
-          std::memcpy(d->m_core.core.p + mc[p], S.core.p + at, (size_t)len * 4);
-          std::memcpy(d->m_core.cvar.p + mc[p], S.cvar.p + at, (size_t)len * 4);
-          std::memcpy(d->m_core.ccon.p + mc[p], S.ccon.p + at, (size_t)len * 4);
-          d->m_core.dirty.emplace_back(mc[p], len);
-        }
-        j += host;
-      }
-      out->inst_off = mi;
-      out->core_off = mc;
-      out->installed = d->m_inst.p;
-      out->core = d->m_core.core.p;
-      out->core_var = d->m_core.cvar.p;
-      out->core_con = d->m_core.ccon.p;
+      if (V.core_len.p[p] > 0 && V.core_off.p[p + 1] > V.core_off.p[p])
+        V.core.dirty.emplace_back(V.core_off.p[p], V.core_len.p[p]);
+  const ResultStage* res = &V;
+  if (nw > 0) {
+    map_host_side(d);
+    res = &d->s;  // all on the host: its layout is the result's
+    if (nw < P) {
+      if (merge_by_problem(d, P)) return fail(d, c);
+      res = &d->m;
     }
   }
+  res->publish(out);
   d->f_which = which;
   d->host_count = nw;
-  out->h2d_bytes = h2d + sh2d;
-  out->d2h_bytes = d2h + sd2h;
+  out->h2d_bytes = c.h2d;
+  out->d2h_bytes = c.d2h;
   out->host_lowered = nw;
   if (dl_times())
     std::fprintf(stderr,
                  "dp_lower_solve: P %d total %.3f ms: lowering wait %.3f plan+submit %.3f host lowering %.3f "
                  "solve wait %.3f merge %.3f (%d on the host)\n",
-                 P, dl_ms() - t0, tm.lower_wait, tm.plan, tm.host, tm.wait, dl_ms() - tmg, nw);
+                 P, dl_ms() - t0, c.lower_wait, c.plan, c.host, c.wait, dl_ms() - tmg, nw);
   return 0;
 }
 

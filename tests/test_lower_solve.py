@@ -10,7 +10,7 @@ import pytest
 
 from deppy_amd import _lib, sat
 from tests import fixtures
-from tests.test_device_lowering import wire_of
+from tests.test_device_lowering import assert_same, wire_of
 from tests.test_lowering import EDGE, V, _random_problems, all_golden_variable_sets, variables_of
 
 pytestmark = pytest.mark.gpu
@@ -184,6 +184,24 @@ def test_fused_reuse_and_malformed_wire(dl):
         dl.lower_solve(_lib.Wire32Arrays(bad))
     got, ref = solve_both(dl, wire)
     assert_equal(got, ref)
+
+
+def test_lower_and_lower_solve_share_a_lowerer(dl, monkeypatch):
+    """dp_lower_device and dp_lower_solve stage the wire in the same device
+    buffers of one lowerer: alternated over batches that change index width
+    and go large, small, large again (the fused calls through both windows),
+    every lowering equals dp_lower_into's byte for byte and every fused
+    result the host-lowered yardstick."""
+    monkeypatch.setenv("DEPPY_FUSED_WINDOW", "256")
+    for config, n, ids16 in ((2, 600, True), (6, 200, False), (3, 900, True), (2, 150, False)):
+        wire = wire_of(config, n, 31)
+        w32 = _lib.Wire32Arrays(wire, ids16=ids16)
+        host = _lib.Lowered(wire, narrow=True, pinned=True, packed=True)
+        ref = yardstick(wire, dl.ctx)
+        assert_same(dl.lower(w32, _lib.Lowered.empty(pinned=True)), host)
+        assert_equal(dl.lower_solve(w32), ref)
+        assert_same(dl.lower(w32, _lib.Lowered.empty(pinned=True)), host)
+        assert dl.host_count == 0
 
 
 def test_fused_byte_accounting(dl):
