@@ -99,6 +99,7 @@ EXPORTS = [
     "dp_plan_footprints", "dp_lds_occupancy",
     "dp_plan_order", "dp_dlower_new", "dp_dlower_free", "dp_lower_device", "dp_dlower_host_count",
     "dp_host_alloc", "dp_host_free", "dp_lower_solve", "dp_dlower_error", "dp_plan_order_heads",
+    "dp_lower_solve_shared", "dp_expand_shared", "dp_expanded_wire", "dp_expanded_free",
 ]
 
 
@@ -290,6 +291,14 @@ def lib():
     L.dp_dlower_host_count.restype = ctypes.c_int64
     L.dp_lower_solve.argtypes = [vp, ctypes.POINTER(Wire32), ctypes.POINTER(Solved)]
     L.dp_dlower_error.argtypes = [vp, ctypes.c_int32, ctypes.POINTER(ctypes.c_char_p)]
+    if hasattr(L, "dp_lower_solve_shared"):  # (an older build loaded as a measurement variant lacks them)
+        L.dp_lower_solve_shared.argtypes = [vp, ctypes.POINTER(Wire32), ctypes.POINTER(Wire32), c_i32p,
+                                            ctypes.POINTER(Solved)]
+        L.dp_expand_shared.argtypes = [ctypes.POINTER(Wire32), ctypes.POINTER(Wire32), c_i32p]
+        L.dp_expand_shared.restype = vp
+        L.dp_expanded_wire.argtypes = [vp]
+        L.dp_expanded_wire.restype = ctypes.POINTER(Wire)
+        L.dp_expanded_free.argtypes = [vp]
     L.dp_plan_order_heads.argtypes = [c_i32p, c_i64p, ctypes.c_int32, ctypes.c_int32, c_i32p, c_i32p]
     L.dp_host_alloc.argtypes = [ctypes.c_int64]
     L.dp_host_alloc.restype = vp
@@ -596,6 +605,30 @@ class Wire32Arrays:
         return w
 
 
+def _query_catalog(queries32: Wire32Arrays, query_catalog) -> np.ndarray:
+    qc = np.ascontiguousarray(query_catalog, np.int32)
+    if qc.ndim != 1 or len(qc) != queries32.n_problems:
+        raise ValueError("query_catalog: one entry per query")
+    return qc if len(qc) else np.zeros(1, np.int32)
+
+
+def expand_shared(catalogs32: Wire32Arrays, queries32: Wire32Arrays, query_catalog) -> WireArrays:
+    """dp_expand_shared: the expanded problems of a shared-catalog call (each
+    its catalog's variables, then the query's) as a 64-bit wire, on the host."""
+    L = lib()
+    qc = _query_catalog(queries32, query_catalog)
+    ks, qs = catalogs32.struct(), queries32.struct()
+    h = L.dp_expand_shared(ctypes.byref(ks), ctypes.byref(qs), _p(qc, c_i32p))
+    if not h:
+        raise ValueError(L.dp_last_global_error().decode())
+    try:
+        d = wire_to_numpy(L.dp_expanded_wire(h).contents)
+    finally:
+        L.dp_expanded_free(h)
+    return WireArrays(d["prob_var_off"], d["var_id"], d["var_con_off"], d["con_kind"], d["con_n"],
+                      d["con_arg_off"], d["con_arg"], d["str_off"], d["str_bytes"].tobytes(), True)
+
+
 class DeviceLowerer:
     """dp_dlower: lowering on the context's first device (dp_lower_device),
     the same records as dp_lower_into, byte for byte."""
@@ -626,6 +659,23 @@ class DeviceLowerer:
         so = Solved()
         if L.dp_lower_solve(self.h, ctypes.byref(ws), ctypes.byref(so)) != 0:
             raise ValueError(L.dp_last_global_error().decode())
+        return self._solved(so)
+
+    def lower_solve_shared(self, catalogs32: Wire32Arrays, queries32: Wire32Arrays, query_catalog) -> dict:
+        """dp_lower_solve_shared: problem p is catalog query_catalog[p]'s
+        variables followed by query p's (-1: the query alone); the catalogs
+        cross PCIe once per call.  -> as lower_solve, on the expanded
+        problems."""
+        L = lib()
+        qc = _query_catalog(queries32, query_catalog)
+        ks, qs = catalogs32.struct(), queries32.struct()
+        so = Solved()
+        if L.dp_lower_solve_shared(self.h, ctypes.byref(ks), ctypes.byref(qs), _p(qc, c_i32p), ctypes.byref(so)) != 0:
+            raise ValueError(L.dp_last_global_error().decode())
+        return self._solved(so)
+
+    def _solved(self, so: Solved) -> dict:
+        L = lib()
         n = so.n_problems
         out = dict(err=_view(self, so.err, n, ctypes.c_int32, np.int32),
                    status=_view(self, so.status, n, ctypes.c_int8, np.int8),

@@ -32,6 +32,12 @@
 // the reported cores are looked up on the device (core_owners.hip).  The
 // fused windows run on the device lowering's own device, the context's
 // first: sharding one wire over several devices is out of scope.
+//
+// dp_lower_solve_shared is dp_lower_solve on problems that begin with a
+// shared catalog: the catalogs' wire is copied to the device once per call,
+// the windows copy only the queries', and the kernel's shared instantiation
+// reads a problem's first variables, constraints and arguments from its
+// catalog and the rest from the query.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -163,8 +169,22 @@ struct DlArgs {
   int32_t* slots;  // [P * DL_SLOT]
   int32_t* ivs;    // [P * DL_C] identity -> variable (last writer)
   int32_t* ics;    // [P * DL_C] identity -> constraint index within the variable
+  // -- the shared instantiation only (dp_lower_solve_shared) --
+  // the catalogs' dp_wire32 on the device, whole (bases and totals as above),
+  // and each problem's catalog (-1: none)
+  const int32_t *kpvo, *kpco, *kpao, *kvid, *kckn, *karg;
+  const uint16_t *kvnc, *kcna, *kvid16, *karg16;
+  int32_t kpbase, kcbase, kabase;
+  int32_t knvars, kncons, knargs;
+  int32_t ncat;
+  const int32_t* qcat;  // [P]
 };
 
+// SHARED: problem p is catalog qcat[p]'s variables followed by its own (the
+// query's), and so its constraints and its arguments.  Every read of the wire
+// goes through the accessors below: an index under the catalog's count reads
+// the catalog's arrays, the rest the query's.
+template <bool SHARED>
 __global__ void __launch_bounds__(DL_T) lower_kernel(DlArgs a) {
   __shared__ DlShared S;
   const int p = a.p0 + (int)blockIdx.x;
@@ -175,22 +195,65 @@ __global__ void __launch_bounds__(DL_T) lower_kernel(DlArgs a) {
       a.nid[p] = 0;
     }
   };
+  // the catalog segment: kv0, kc0, ka0 its first variable, constraint and
+  // argument, nvk, Ck, Ak their counts (none: all 0)
+  int kv0 = 0, kc0 = 0, ka0 = 0, nvk = 0, Ck = 0, Ak = 0;
+  if constexpr (SHARED) {
+    const int b = a.qcat[p];
+    if (b < -1 || b >= a.ncat) return give_up();
+    if (b >= 0) {
+      kv0 = a.kpvo[b] - a.kpbase;
+      kc0 = a.kpco[b] - a.kcbase;
+      ka0 = a.kpao[b] - a.kabase;
+      const int kv1 = a.kpvo[b + 1] - a.kpbase, kc1 = a.kpco[b + 1] - a.kcbase, ka1 = a.kpao[b + 1] - a.kabase;
+      nvk = kv1 - kv0;
+      Ck = kc1 - kc0;
+      Ak = ka1 - ka0;
+      if (kv0 < 0 || nvk < 0 || kv1 > a.knvars || nvk > DL_NV || kc0 < 0 || Ck < 0 || kc1 > a.kncons || Ck > DL_C ||
+          ka0 < 0 || Ak < 0 || ka1 > a.knargs || Ak > DL_A)
+        return give_up();
+    }
+  }
   const int v0 = a.pvo[p] - a.pbase, v1 = a.pvo[p + 1] - a.pbase;
-  const int nv = v1 - v0;
+  if (SHARED && (v1 < v0 || v1 - v0 > DL_NV)) return give_up();
+  const int nv = nvk + (v1 - v0);
   if (nv <= 0 || nv > DL_NV || v0 < 0 || v1 > a.nvars) return give_up();
   const int cb = a.pco[p] - a.cbase, ce = a.pco[p + 1] - a.cbase;
-  const int C = ce - cb;
+  if (SHARED && (ce < cb || ce - cb > DL_C)) return give_up();
+  const int C = Ck + (ce - cb);
   if (cb < 0 || C < 0 || ce > a.ncons || C > DL_C) return give_up();
   const int ab = a.pao[p] - a.abase, ae = a.pao[p + 1] - a.abase;
-  const int A = ae - ab;
+  if (SHARED && (ae < ab || ae - ab > DL_A)) return give_up();
+  const int A = Ak + (ae - ab);
   if (ab < 0 || A < 0 || ae > a.nargs || A > DL_A) return give_up();
+  // the wire's reads: variable i, constraint c and argument j of the problem
+  auto w_vnc = [&](int i) -> int {
+    if (SHARED && i < nvk) return (int)a.kvnc[kv0 + i];
+    return (int)a.vnc[v0 + (i - nvk)];
+  };
+  auto w_vid = [&](int i) -> int32_t {
+    if (SHARED && i < nvk) return a.ids16 ? (int32_t)a.kvid16[kv0 + i] : a.kvid[kv0 + i];
+    return a.ids16 ? (int32_t)a.vid16[v0 + (i - nvk)] : a.vid[v0 + (i - nvk)];
+  };
+  auto w_cna = [&](int c) -> int {
+    if (SHARED && c < Ck) return (int)a.kcna[kc0 + c];
+    return (int)a.cna[cb + (c - Ck)];
+  };
+  auto w_ckn = [&](int c) -> int32_t {
+    if (SHARED && c < Ck) return a.kckn[kc0 + c];
+    return a.ckn[cb + (c - Ck)];
+  };
+  auto w_arg = [&](int j) -> int32_t {
+    if (SHARED && j < Ak) return a.ids16 ? (int32_t)a.karg16[ka0 + j] : a.karg[ka0 + j];
+    return a.ids16 ? (int32_t)a.arg16[ab + (j - Ak)] : a.arg[ab + (j - Ak)];
+  };
   // the counts -> offsets within the problem (their sums must be C and A)
   {
     int run = 0;
     for (int i0 = 0; i0 < nv && run <= C; i0 += DL_T) {
       const int i = i0 + lane;
       int tot;
-      const int ex = excl_scan(i < nv ? (int)a.vnc[v0 + i] : 0, tot);
+      const int ex = excl_scan(i < nv ? w_vnc(i) : 0, tot);
       if (i < nv) S.vstart[i] = (int16_t)min(run + ex, 0x7fff);
       run += tot;
     }
@@ -198,7 +261,7 @@ __global__ void __launch_bounds__(DL_T) lower_kernel(DlArgs a) {
     for (int c0 = 0; c0 < C && arun <= A; c0 += DL_T) {
       const int c = c0 + lane;
       int tot;
-      const int ex = excl_scan(c < C ? (int)a.cna[cb + c] : 0, tot);
+      const int ex = excl_scan(c < C ? w_cna(c) : 0, tot);
       if (c < C) S.castart[c] = (int16_t)min(arun + ex, 0x7fff);
       arun += tot;
     }
@@ -206,6 +269,10 @@ __global__ void __launch_bounds__(DL_T) lower_kernel(DlArgs a) {
     if (lane == 0) {
       S.vstart[nv] = (int16_t)C;
       S.castart[C] = (int16_t)A;
+    }
+    if constexpr (SHARED) {  // each segment's counts add up to its own ranges
+      __syncthreads();
+      if (S.vstart[nvk] != Ck || S.castart[Ck] != Ak) return give_up();
     }
   }
 
@@ -227,12 +294,12 @@ __global__ void __launch_bounds__(DL_T) lower_kernel(DlArgs a) {
 
   // ---- 1. identifiers -> variables (lit_mapping.go:50-57) ----
   for (int i = lane; i < nv; i += DL_T) {
-    const int32_t sid = a.ids16 ? (int32_t)a.vid16[v0 + i] : a.vid[v0 + i];
+    const int32_t sid = w_vid(i);
     if (sid < 0 || (int64_t)sid >= a.n_strs) {
       S.fb = 1;  // malformed: the host reports it
       continue;
     }
-    for (int c = S.vstart[i], c1 = S.vstart[i] + (int)a.vnc[v0 + i]; c < c1; ++c) S.cs[c] = (int16_t)i;
+    for (int c = S.vstart[i], c1 = S.vstart[i] + w_vnc(i); c < c1; ++c) S.cs[c] = (int16_t)i;
     uint32_t h = ((uint32_t)sid * 2654435761u) >> 22;  // log2(DL_VH) bits
     for (;;) {
       const int32_t old = atomicCAS(&S.vkey[h], 0, sid + 1);
@@ -251,7 +318,7 @@ __global__ void __launch_bounds__(DL_T) lower_kernel(DlArgs a) {
   if (S.fb) return give_up();
   // arguments (LitOf, lit_mapping.go:81-88: an unknown one is an error the host reports)
   for (int j = lane; j < A; j += DL_T) {
-    const int32_t sid = a.ids16 ? (int32_t)a.arg16[ab + j] : a.arg[ab + j];
+    const int32_t sid = w_arg(j);
     if (sid < 0 || (int64_t)sid >= a.n_strs) {
       S.fb = 1;
       continue;
@@ -275,7 +342,7 @@ __global__ void __launch_bounds__(DL_T) lower_kernel(DlArgs a) {
 
   // ---- 2. identity keys (lower.cpp lower_fast's switch) ----
   for (int c = lane; c < C; c += DL_T) {
-    const int32_t kn = a.ckn[cb + c];
+    const int32_t kn = w_ckn(c);
     const int kind = kn & 7;
     const int n = kn >> 3;
     const int a0 = S.castart[c], a1 = S.castart[c + 1];
@@ -424,7 +491,7 @@ __global__ void __launch_bounds__(DL_T) lower_kernel(DlArgs a) {
     if (s >= 0 && !isf && m_hashed(m)) {
       const int f0 = S.castart[first], fns = S.castart[first + 1] - f0;
       bad = fns != ns || (kind == DP_DEPENDENCY && S.cs[first] != vi) ||
-            (kind == DP_ATMOST && a.ckn[cb + first] != a.ckn[cb + c]) || m_kind(S.cmeta[first]) != kind;
+            (kind == DP_ATMOST && w_ckn(first) != w_ckn(c)) || m_kind(S.cmeta[first]) != kind;
       for (int j = 0; j < ns && !bad; ++j) bad = S.ca[f0 + j] != S.ca[a0 + j];
     }
     if (__ballot(bad)) {
@@ -483,7 +550,7 @@ __global__ void __launch_bounds__(DL_T) lower_kernel(DlArgs a) {
     }
     bool kb1 = true;
     if (isk) {
-      const int n = a.ckn[cb + c] >> 3;
+      const int n = w_ckn(c) >> 3;
       S.klen[krow] = (uint8_t)rlen;
       S.kb[krow] = (int16_t)n;
       kb1 = n == 1;
@@ -821,15 +888,81 @@ struct MapBuf {
   }
 };
 
+// A call's input: a wire on its own (dp_lower_device, dp_lower_solve), or
+// the queries' wire with the catalogs' and each query's catalog
+// (dp_lower_solve_shared).  Problem p is then catalog qc[p]'s variables
+// followed by query p's; the sizes below are that expanded problem's.
+struct WireIn {
+  const dp_wire32* w = nullptr;    // the problems (the queries)
+  const dp_wire32* cat = nullptr;  // the catalogs, or NULL
+  const int32_t* qc = nullptr;     // [w->n_problems] -1..cat->n_problems-1
+  int32_t catalog(int32_t p) const { return cat ? qc[p] : -1; }
+  int64_t nv(int32_t p) const {
+    const int32_t b = catalog(p);
+    return (int64_t)w->prob_var_off[p + 1] - w->prob_var_off[p] +
+           (b >= 0 ? (int64_t)cat->prob_var_off[b + 1] - cat->prob_var_off[b] : 0);
+  }
+  int64_t nc(int32_t p) const {
+    const int32_t b = catalog(p);
+    return (int64_t)w->prob_con_off[p + 1] - w->prob_con_off[p] +
+           (b >= 0 ? (int64_t)cat->prob_con_off[b + 1] - cat->prob_con_off[b] : 0);
+  }
+  int64_t na(int32_t p) const {
+    const int32_t b = catalog(p);
+    return (int64_t)w->prob_arg_off[p + 1] - w->prob_arg_off[p] +
+           (b >= 0 ? (int64_t)cat->prob_arg_off[b + 1] - cat->prob_arg_off[b] : 0);
+  }
+  // problem p's segments in order: (wire, problem) pairs, at most two
+  struct Seg {
+    const dp_wire32* w;
+    int32_t p;
+  };
+  int segs(int32_t p, Seg s[2]) const {
+    int n = 0;
+    const int32_t b = catalog(p);
+    if (b >= 0) s[n++] = Seg{cat, b};
+    s[n++] = Seg{w, p};
+    return n;
+  }
+};
+
+// The catalogs' wire on the device, whole: copied once per call, read by
+// every window's lowering.
+struct CatStage {
+  DevBuf<int32_t> pvo, pco, pao, vid, ckn, arg;
+  DevBuf<uint16_t> vnc, cna, vid16, arg16;
+  int32_t n = 0, pbase = 0, cbase = 0, abase = 0, nvars = 0, ncons = 0, nargs = 0;
+  void fill(DlArgs& a) const {
+    a.kpvo = pvo.p;
+    a.kpco = pco.p;
+    a.kpao = pao.p;
+    a.kvid = vid.p;
+    a.kvnc = vnc.p;
+    a.kckn = ckn.p;
+    a.kcna = cna.p;
+    a.karg = arg.p;
+    a.kvid16 = vid16.p;
+    a.karg16 = arg16.p;
+    a.kpbase = pbase;
+    a.kcbase = cbase;
+    a.kabase = abase;
+    a.knvars = nvars;
+    a.kncons = ncons;
+    a.knargs = nargs;
+    a.ncat = n;
+  }
+};
+
 // The device copy of one range of a wire's problems and the lowering's
 // outputs for it (a slot and the identity owners per problem).
 struct WireStage {
   DevBuf<int32_t> pvo, pco, pao, vid, ckn, arg, words, nid, slots, ivs, ics;
   DevBuf<uint16_t> vnc, cna, vid16, arg16;
-  hipError_t reserve(size_t n, size_t nvars, size_t ncons, size_t nargs, bool ids16) {
+  DevBuf<int32_t> qcat;  // the range's slice of query_catalog (shared input)
+  hipError_t reserve(size_t n, size_t nvars, size_t ncons, size_t nargs, bool ids16, bool shared) {
     hipError_t e = hipSuccess;
     auto ok = [&e](hipError_t r) { return (e = r) == hipSuccess; };
-    (void)(ok(pvo.need(n + 1)) && ok(pco.need(n + 1)) && ok(pao.need(n + 1)) &&
+    (void)((!shared || ok(qcat.need(n))) && ok(pvo.need(n + 1)) && ok(pco.need(n + 1)) && ok(pao.need(n + 1)) &&
            (ids16 ? ok(vid16.need(nvars + 1)) && ok(arg16.need(nargs + 1))
                   : ok(vid.need(nvars + 1)) && ok(arg.need(nargs + 1))) &&
            ok(vnc.need(nvars + 1)) && ok(ckn.need(ncons + 1)) && ok(cna.need(ncons + 1)) && ok(words.need(n)) &&
@@ -837,7 +970,7 @@ struct WireStage {
     return e;
   }
   template <class F>
-  int64_t enqueue(dp_dlower* d, const dp_wire32* w, int32_t q0, int32_t q1, F after_piece);
+  int64_t enqueue(dp_dlower* d, const WireIn& in, int32_t q0, int32_t q1, F after_piece);
 };
 
 // One window of the fused path: the window's wire ranges, its slots and
@@ -918,6 +1051,14 @@ struct ResultStage {
   }
 };
 
+// The arrays of a 64-bit dp_wire gathered from a compact one (host_subwire).
+struct SubStore {
+  std::vector<int64_t> s_pvo, s_vid, s_vco, s_cao, s_arg;
+  std::vector<int32_t> s_kind, s_cn;
+  std::vector<uint8_t> s_bad;
+  std::vector<int64_t> s_sz, s_off;
+};
+
 constexpr int32_t kFusedWindow = 16384;  // problems per window: 320 MiB of slots and owners at most
 
 }  // namespace
@@ -928,6 +1069,7 @@ struct dp_dlower {
   // The two windows of dp_lower_solve.  dp_lower_device stages in fw[0].wire:
   // one call runs at a time, and dp_lower_solve leaves no job behind.
   FusedWin fw[2];
+  CatStage cat;  // dp_lower_solve_shared: the catalogs
   std::vector<int64_t> f_rec_off;  // [window + 1]: slot i at i * DL_SLOT
   // -- dp_lower_solve --
   PinBuf<int32_t> o_err;
@@ -950,10 +1092,7 @@ struct dp_dlower {
   int64_t host_count = 0;
   // the problems lowered on the host, as a dp_wire of their own
   std::vector<int32_t> which;
-  std::vector<int64_t> s_pvo, s_vid, s_vco, s_cao, s_arg;
-  std::vector<int32_t> s_kind, s_cn;
-  std::vector<uint8_t> s_bad;
-  std::vector<int64_t> s_sz, s_off;
+  SubStore sub;
   std::mutex mu;  // one call at a time
   ~dp_dlower() {
     if (side) dp_lowered_free(side);
@@ -994,19 +1133,23 @@ void drain(dp_dlower* d) {
 }
 #define DL_OK_DRAIN(expr) DL_OK_OR(expr, drain(d))
 
-// Enqueue the copy and the lowering of w's problems [q0, q1) into this stage,
-// the range as a batch of its own (offsets from its first element).  Behind
+// Enqueue the copy and the lowering of in.w's problems [q0, q1) into this
+// stage, the range as a batch of its own (offsets from its first element).
+// With catalogs (already enqueued on the copy stream, d->cat) only the
+// queries' ranges and the range's slice of query_catalog are copied.  Behind
 // each piece [r0, r1)'s lowering, after_piece(r0, r1) enqueues what the
 // caller has to follow it and returns a hipError_t.  Returns the bytes copied
 // to the device, or -1.
 template <class F>
-int64_t WireStage::enqueue(dp_dlower* d, const dp_wire32* w, int32_t q0, int32_t q1, F after_piece) {
+int64_t WireStage::enqueue(dp_dlower* d, const WireIn& in, int32_t q0, int32_t q1, F after_piece) {
+  const dp_wire32* const w = in.w;
+  const bool shared = in.cat != nullptr;
   const int32_t n = q1 - q0;
   const int32_t pv0 = w->prob_var_off[q0], cb0 = w->prob_con_off[q0], ab0 = w->prob_arg_off[q0];
   const int32_t nvars = w->prob_var_off[q1] - pv0, ncons = w->prob_con_off[q1] - cb0,
                 nargs = w->prob_arg_off[q1] - ab0;
   const bool ids16 = w->var_id16 != nullptr;
-  DL_OK(reserve((size_t)n, (size_t)nvars, (size_t)ncons, (size_t)nargs, ids16));
+  DL_OK(reserve((size_t)n, (size_t)nvars, (size_t)ncons, (size_t)nargs, ids16, shared));
   hipStream_t st = d->st, cst = d->cst;
   int64_t bytes = 0;
   auto h2d = [&](auto* dst, const auto* src, int64_t m) {
@@ -1016,6 +1159,7 @@ int64_t WireStage::enqueue(dp_dlower* d, const dp_wire32* w, int32_t q0, int32_t
   DL_OK(h2d(pvo.p, w->prob_var_off + q0, (int64_t)n + 1));
   DL_OK(h2d(pco.p, w->prob_con_off + q0, (int64_t)n + 1));
   DL_OK(h2d(pao.p, w->prob_arg_off + q0, (int64_t)n + 1));
+  if (shared) DL_OK(h2d(qcat.p, in.qc + q0, (int64_t)n));
   DlArgs a{};
   a.pvo = pvo.p;
   a.pco = pco.p;
@@ -1041,6 +1185,10 @@ int64_t WireStage::enqueue(dp_dlower* d, const dp_wire32* w, int32_t q0, int32_t
   a.slots = slots.p;
   a.ivs = ivs.p;
   a.ics = ics.p;
+  if (shared) {
+    d->cat.fill(a);
+    a.qcat = qcat.p;
+  }
   // pieces: the wire's copy of piece k+1 runs under the lowering (and what
   // follows it) of piece k.  Every copy and its event is enqueued first: an
   // event marker may share a hardware queue with the packing's stream, and
@@ -1066,93 +1214,111 @@ int64_t WireStage::enqueue(dp_dlower* d, const dp_wire32* w, int32_t q0, int32_t
     DL_OK(hipStreamWaitEvent(st, d->ev[k], 0));
     if (r1 == r0) continue;
     a.p0 = r0 - q0;
-    hipLaunchKernelGGL(lower_kernel, dim3((unsigned)(r1 - r0)), dim3(DL_T), 0, st, a);
+    if (shared) hipLaunchKernelGGL(lower_kernel<true>, dim3((unsigned)(r1 - r0)), dim3(DL_T), 0, st, a);
+    else hipLaunchKernelGGL(lower_kernel<false>, dim3((unsigned)(r1 - r0)), dim3(DL_T), 0, st, a);
     DL_OK(hipGetLastError());
     DL_OK(after_piece(r0, r1));
   }
   return bytes;
 }
 
-// The problems d->which of w as a dp_wire of their own (64-bit, offsets
-// from 0).  Inconsistent counts stay malformed (a negative identifier), so
-// the host lowering reports the batch as dp_lower_into does.
-void host_subwire(dp_dlower* d, const dp_wire32* w, dp_wire* sub) {
-  const int64_t nw = (int64_t)d->which.size();
+// Problems `which` of `in` as a dp_wire of their own (64-bit, offsets from
+// 0, arrays in st), each expanded: its catalog's variables, then its own.
+// Inconsistent counts in either segment stay malformed (a negative
+// identifier), so the host lowering reports the batch as dp_lower_into does.
+void host_subwire(SubStore& st, const std::vector<int32_t>& which, const WireIn& in, dp_wire* sub) {
+  const int64_t nw = (int64_t)which.size();
   dp::Pool& pool = dp::host_pool();
   // (a few large problems still spread over the pool: config 4's catalogs)
   const int64_t blk = std::max<int64_t>(1, std::min<int64_t>(64, nw / (4 * (int64_t)pool.size())));
   // sizes (on the host pool): a problem whose counts do not add up to its
   // ranges becomes one malformed variable
-  std::vector<int64_t>& sz = d->s_sz;  // [3 nw]: variables, constraints, arguments
+  std::vector<int64_t>& sz = st.s_sz;  // [3 nw]: variables, constraints, arguments
   sz.resize((size_t)(3 * nw + 3));
-  std::vector<uint8_t>& bad = d->s_bad;
+  std::vector<uint8_t>& bad = st.s_bad;
   bad.assign((size_t)nw, 0);
   pool.run(nw, std::function<void(int64_t)>([&](int64_t i) {
-    const int32_t p = d->which[(size_t)i];
-    const int32_t v0 = w->prob_var_off[p], v1 = w->prob_var_off[p + 1];
-    const int64_t c0 = w->prob_con_off[p], ce = w->prob_con_off[p + 1];
-    const int64_t x0 = w->prob_arg_off[p], xe = w->prob_arg_off[p + 1];
-    int64_t sc = 0, sx = 0;
-    for (int32_t v = v0; v < v1; ++v) sc += w->var_ncon[v];
-    if (sc == ce - c0)
-      for (int64_t k = c0; k < ce; ++k) sx += w->con_nargs[k];
-    const bool b = sc != ce - c0 || sx != xe - x0;
+    WireIn::Seg sg[2];
+    const int ns = in.segs(which[(size_t)i], sg);
+    bool b = false;
+    int64_t tv = 0, tc = 0, tx = 0;
+    for (int g = 0; g < ns; ++g) {
+      const dp_wire32* w = sg[g].w;
+      const int32_t p = sg[g].p;
+      const int32_t v0 = w->prob_var_off[p], v1 = w->prob_var_off[p + 1];
+      const int64_t c0 = w->prob_con_off[p], ce = w->prob_con_off[p + 1];
+      const int64_t x0 = w->prob_arg_off[p], xe = w->prob_arg_off[p + 1];
+      int64_t sc = 0, sx = 0;
+      for (int32_t v = v0; v < v1; ++v) sc += w->var_ncon[v];
+      if (sc == ce - c0)
+        for (int64_t k = c0; k < ce; ++k) sx += w->con_nargs[k];
+      b = b || sc != ce - c0 || sx != xe - x0;
+      tv += v1 - v0;
+      tc += ce - c0;
+      tx += xe - x0;
+    }
     bad[(size_t)i] = b;
-    sz[(size_t)(3 * i)] = b ? std::max(1, v1 - v0) : v1 - v0;
-    sz[(size_t)(3 * i + 1)] = b ? 0 : ce - c0;
-    sz[(size_t)(3 * i + 2)] = b ? 0 : xe - x0;
+    sz[(size_t)(3 * i)] = b ? std::max<int64_t>(1, tv) : tv;
+    sz[(size_t)(3 * i + 1)] = b ? 0 : tc;
+    sz[(size_t)(3 * i + 2)] = b ? 0 : tx;
   }), blk);
   // offsets (serial), then the arrays (on the pool)
-  std::vector<int64_t>& off = d->s_off;  // [3 (nw+1)]
+  std::vector<int64_t>& off = st.s_off;  // [3 (nw+1)]
   off.resize((size_t)(3 * nw + 3));
   off[0] = off[1] = off[2] = 0;
   for (int64_t i = 0; i < nw; ++i)
     for (int q = 0; q < 3; ++q) off[(size_t)(3 * (i + 1) + q)] = off[(size_t)(3 * i + q)] + sz[(size_t)(3 * i + q)];
   const int64_t tv = off[(size_t)(3 * nw)], tc = off[(size_t)(3 * nw + 1)], ta = off[(size_t)(3 * nw + 2)];
-  d->s_pvo.resize((size_t)nw + 1);
-  d->s_vid.resize((size_t)tv + 1);
-  d->s_vco.resize((size_t)tv + 1);
-  d->s_kind.resize((size_t)tc + 1);
-  d->s_cn.resize((size_t)tc + 1);
-  d->s_cao.resize((size_t)tc + 1);
-  d->s_arg.resize((size_t)ta + 1);
-  int64_t* const pvo = d->s_pvo.data();
-  int64_t* const vid = d->s_vid.data();
-  int64_t* const vco = d->s_vco.data();
-  int32_t* const kind = d->s_kind.data();
-  int32_t* const cn = d->s_cn.data();
-  int64_t* const cao = d->s_cao.data();
-  int64_t* const arg = d->s_arg.data();
+  st.s_pvo.resize((size_t)nw + 1);
+  st.s_vid.resize((size_t)tv + 1);
+  st.s_vco.resize((size_t)tv + 1);
+  st.s_kind.resize((size_t)tc + 1);
+  st.s_cn.resize((size_t)tc + 1);
+  st.s_cao.resize((size_t)tc + 1);
+  st.s_arg.resize((size_t)ta + 1);
+  int64_t* const pvo = st.s_pvo.data();
+  int64_t* const vid = st.s_vid.data();
+  int64_t* const vco = st.s_vco.data();
+  int32_t* const kind = st.s_kind.data();
+  int32_t* const cn = st.s_cn.data();
+  int64_t* const cao = st.s_cao.data();
+  int64_t* const arg = st.s_arg.data();
   for (int64_t i = 0; i <= nw; ++i) pvo[i] = off[(size_t)(3 * i)];
   pool.run(nw, std::function<void(int64_t)>([&](int64_t i) {
-    const int32_t p = d->which[(size_t)i];
-    const int32_t v0 = w->prob_var_off[p], v1 = w->prob_var_off[p + 1];
     int64_t nv = off[(size_t)(3 * i)], nc = off[(size_t)(3 * i + 1)], na = off[(size_t)(3 * i + 2)];
     if (bad[(size_t)i]) {
-      for (int32_t v = v0; v < std::max(v1, v0 + 1); ++v) {
+      for (int64_t v = 0; v < sz[(size_t)(3 * i)]; ++v) {
         vid[nv] = -1;  // (a negative identifier: dp_lower_into reports the batch malformed)
         vco[nv++] = nc;
       }
       return;
     }
-    int64_t c = w->prob_con_off[p];
-    const int64_t xb = w->prob_arg_off[p];
-    int64_t x = 0;
-    for (int32_t v = v0; v < v1; ++v) {
-      vid[nv] = w->var_id16 ? (int64_t)w->var_id16[v] : (int64_t)w->var_id[v];
-      vco[nv++] = nc;
-      for (int32_t k = 0; k < (int32_t)w->var_ncon[v]; ++k, ++c) {
-        const int32_t kn = w->con_kn[c];
-        kind[nc] = kn & 7;
-        cn[nc] = kn >> 3;
-        cao[nc++] = na;
-        for (int32_t j = 0; j < (int32_t)w->con_nargs[c]; ++j, ++x)
-          arg[na++] = w->con_arg16 ? (int64_t)w->con_arg16[xb + x] : (int64_t)w->con_arg[xb + x];
+    WireIn::Seg sg[2];
+    const int ns = in.segs(which[(size_t)i], sg);
+    for (int g = 0; g < ns; ++g) {
+      const dp_wire32* w = sg[g].w;
+      const int32_t p = sg[g].p;
+      const int32_t v0 = w->prob_var_off[p], v1 = w->prob_var_off[p + 1];
+      int64_t c = w->prob_con_off[p];
+      const int64_t xb = w->prob_arg_off[p];
+      int64_t x = 0;
+      for (int32_t v = v0; v < v1; ++v) {
+        vid[nv] = w->var_id16 ? (int64_t)w->var_id16[v] : (int64_t)w->var_id[v];
+        vco[nv++] = nc;
+        for (int32_t k = 0; k < (int32_t)w->var_ncon[v]; ++k, ++c) {
+          const int32_t kn = w->con_kn[c];
+          kind[nc] = kn & 7;
+          cn[nc] = kn >> 3;
+          cao[nc++] = na;
+          for (int32_t j = 0; j < (int32_t)w->con_nargs[c]; ++j, ++x)
+            arg[na++] = w->con_arg16 ? (int64_t)w->con_arg16[xb + x] : (int64_t)w->con_arg[xb + x];
+        }
       }
     }
   }), blk);
   vco[tv] = tc;
   cao[tc] = ta;
+  const dp_wire32* w = in.w;
   sub->n_problems = (int32_t)nw;
   sub->prob_var_off = pvo;
   sub->var_id = vid;
@@ -1172,7 +1338,9 @@ int lower_on_host(const dp_wire32* w, int32_t flags, dp_lowered* lw, dp_dlower* 
   d->which.resize((size_t)w->n_problems);
   for (int32_t p = 0; p < w->n_problems; ++p) d->which[(size_t)p] = p;
   dp_wire sub{};
-  host_subwire(d, w, &sub);
+  WireIn in;
+  in.w = w;
+  host_subwire(d->sub, d->which, in, &sub);
   d->host_count = w->n_problems;
   return dp_lower_into(&sub, flags, lw);
 }
@@ -1192,13 +1360,13 @@ bool dl_times() {
 // Problems past the kernel's sizes are lowered on the host: when they hold
 // most of the batch's arguments, the whole batch is (a device pass and a
 // splice would only add to the host's work).
-bool device_takes(const dp_wire32* w) {
-  const int32_t P = w->n_problems;
-  int64_t fit_args = 0, all_args = (int64_t)w->prob_arg_off[P] - w->prob_arg_off[0];
+// (With catalogs, a problem's sizes are its expanded ones.)
+bool device_takes(const WireIn& in) {
+  const int32_t P = in.w->n_problems;
+  int64_t fit_args = 0, all_args = 0;
   for (int32_t p = 0; p < P; ++p) {
-    const int32_t nv = w->prob_var_off[p + 1] - w->prob_var_off[p];
-    const int32_t nc = w->prob_con_off[p + 1] - w->prob_con_off[p];
-    const int32_t na = w->prob_arg_off[p + 1] - w->prob_arg_off[p];
+    const int64_t nv = in.nv(p), nc = in.nc(p), na = in.na(p);
+    all_args += na;
     if (nv >= 1 && nv <= DL_NV && nc <= DL_C && na <= DL_A) fit_args += na + 1;
   }
   return 2 * fit_args >= all_args + P;
@@ -1280,7 +1448,9 @@ int dp_lower_device(dp_dlower* d, const dp_wire32* w, int32_t flags, dp_lowered*
   const bool ours = (flags & (DP_LOWER_NARROW | DP_LOWER_PACKED)) == (DP_LOWER_NARROW | DP_LOWER_PACKED) &&
                     !(flags & DP_LOWER_NO_P8) && dp::ldsg_env() != dp::LDSG_ALWAYS && P > 0;
   if (!ours) return lower_on_host(w, flags, lw, d);
-  if (!device_takes(w)) return lower_on_host(w, flags, lw, d);
+  WireIn in;
+  in.w = w;
+  if (!device_takes(in)) return lower_on_host(w, flags, lw, d);
   if (fault != WIRE_OK) return dl_fail("dp_lower: malformed wire batch");
   const int64_t nvars = w->prob_var_off[P] - w->prob_var_off[0], ncons = w->prob_con_off[P] - w->prob_con_off[0],
                 nargs = w->prob_arg_off[P] - w->prob_arg_off[0];
@@ -1321,7 +1491,7 @@ int dp_lower_device(dp_dlower* d, const dp_wire32* w, int32_t flags, dp_lowered*
   WireStage& S = d->fw[0].wire;
   hipStream_t st = d->st, pst = d->pst;
   int k = 0;
-  const int64_t copied = S.enqueue(d, w, 0, P, [&](int32_t r0, int32_t r1) {
+  const int64_t copied = S.enqueue(d, in, 0, P, [&](int32_t r0, int32_t r1) {
     hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(SCAN_T), 0, st, S.words.p, S.nid.p, r0, r1, d->ro.p, d->io.p);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipEventRecord(d->es[k], st);
@@ -1364,7 +1534,7 @@ int dp_lower_device(dp_dlower* d, const dp_wire32* w, int32_t flags, dp_lowered*
     return 0;
   }
   dp_wire sub{};
-  host_subwire(d, w, &sub);
+  host_subwire(d->sub, d->which, in, &sub);
   const double t_sub = dl_ms();
   if (dp::lowered_splice(lw, &sub, flags, d->which.data(), (int32_t)d->which.size()) != 0)
     return dl_fail("dp_lower: malformed wire batch");
@@ -1389,10 +1559,54 @@ struct FusedCall {
   double lower_wait = 0, plan = 0, host = 0, wait = 0;  // ms
 };
 
+// The catalogs' wire to the device, whole, on the copy stream.  Returns the
+// bytes copied, or -1.
+int64_t upload_catalogs(dp_dlower* d, const dp_wire32* k) {
+  CatStage& K = d->cat;
+  const int32_t B = k->n_problems;
+  const bool ids16 = k->var_id16 != nullptr;
+  K.n = B;
+  K.pbase = k->prob_var_off[0];
+  K.cbase = k->prob_con_off[0];
+  K.abase = k->prob_arg_off[0];
+  K.nvars = k->prob_var_off[B] - K.pbase;
+  K.ncons = k->prob_con_off[B] - K.cbase;
+  K.nargs = k->prob_arg_off[B] - K.abase;
+  DL_OK(K.pvo.need((size_t)B + 1));
+  DL_OK(K.pco.need((size_t)B + 1));
+  DL_OK(K.pao.need((size_t)B + 1));
+  if (ids16) {
+    DL_OK(K.vid16.need((size_t)K.nvars + 1));
+    DL_OK(K.arg16.need((size_t)K.nargs + 1));
+  } else {
+    DL_OK(K.vid.need((size_t)K.nvars + 1));
+    DL_OK(K.arg.need((size_t)K.nargs + 1));
+  }
+  DL_OK(K.vnc.need((size_t)K.nvars + 1));
+  DL_OK(K.ckn.need((size_t)K.ncons + 1));
+  DL_OK(K.cna.need((size_t)K.ncons + 1));
+  int64_t bytes = 0;
+  auto h2d = [&](auto* dst, const auto* src, int64_t m) {
+    bytes += m > 0 ? m * (int64_t)sizeof(*src) : 0;
+    return m > 0 ? hipMemcpyAsync(dst, src, (size_t)m * sizeof(*src), hipMemcpyHostToDevice, d->cst) : hipSuccess;
+  };
+  DL_OK(h2d(K.pvo.p, k->prob_var_off, (int64_t)B + 1));
+  DL_OK(h2d(K.pco.p, k->prob_con_off, (int64_t)B + 1));
+  DL_OK(h2d(K.pao.p, k->prob_arg_off, (int64_t)B + 1));
+  if (ids16) DL_OK(h2d(K.vid16.p, k->var_id16 + K.pbase, K.nvars));
+  else DL_OK(h2d(K.vid.p, k->var_id + K.pbase, K.nvars));
+  DL_OK(h2d(K.vnc.p, k->var_ncon + K.pbase, K.nvars));
+  DL_OK(h2d(K.ckn.p, k->con_kn + K.cbase, K.ncons));
+  DL_OK(h2d(K.cna.p, k->con_nargs + K.cbase, K.ncons));
+  if (ids16) DL_OK(h2d(K.arg16.p, k->con_arg16 + K.abase, K.nargs));
+  else DL_OK(h2d(K.arg.p, k->con_arg + K.abase, K.nargs));
+  return bytes;
+}
+
 // Enqueue the wire copy, the lowering and the header kernel of window
 // [q0, q1) into B, recording B.lowered behind them.  Returns the bytes copied
 // to the device, or -1.
-int64_t enqueue_window(dp_dlower* d, FusedWin& B, const dp_wire32* w, int32_t q0, int32_t q1) {
+int64_t enqueue_window(dp_dlower* d, FusedWin& B, const WireIn& w, int32_t q0, int32_t q1) {
   const int32_t n = q1 - q0;
   B.q0 = q0;
   B.n = n;
@@ -1488,17 +1702,19 @@ int submit_window(dp_dlower* d, FusedWin& B, int64_t inst_cap, int64_t core_cap)
 // A batch of several windows alternates two buffers of half a window each, so
 // window k+1 is copied and lowered under window k's solve.  Their jobs are
 // left in flight.
-int run_windows(dp_dlower* d, const dp_wire32* w, FusedCall& c) {
+int run_windows(dp_dlower* d, const WireIn& in, FusedCall& c) {
   if (hipSetDevice(d->dev) != hipSuccess) return dl_fail("dp_lower_solve: hipSetDevice failed");
-  const int32_t P = w->n_problems;
+  const int32_t P = in.w->n_problems;
   const int32_t W = fused_window();
   const int32_t win = P <= W ? P : std::max<int32_t>(1, W / 2);
   const int32_t nwin = (P + win - 1) / win;
   // staging of the windows' results, sized from the wire's totals (a bitmap
   // word per 32 variables, an identity per constraint at most)
-  const int64_t core_cap = w->prob_con_off[P] - w->prob_con_off[0];
-  int64_t inst_cap = 0;
-  for (int32_t p = 0; p < P; ++p) inst_cap += dp::bits_words(w->prob_var_off[p + 1] - w->prob_var_off[p]);
+  int64_t core_cap = 0, inst_cap = 0;
+  for (int32_t p = 0; p < P; ++p) {
+    core_cap += in.nc(p);
+    inst_cap += dp::bits_words((int32_t)std::min<int64_t>(in.nv(p), INT32_MAX));
+  }
   if (!d->v.need_data((size_t)inst_cap, (size_t)core_cap))
     return dl_fail("dp_lower_solve: page-locked allocation failed");
   if (d->f_rec_off.size() < (size_t)win + 1) {
@@ -1507,10 +1723,15 @@ int run_windows(dp_dlower* d, const dp_wire32* w, FusedCall& c) {
   }
   auto enqueue = [&](int k) {
     const int32_t q0 = k * win, q1 = (int32_t)std::min<int64_t>(P, (int64_t)q0 + win);
-    const int64_t b = enqueue_window(d, d->fw[k & 1], w, q0, q1);
+    const int64_t b = enqueue_window(d, d->fw[k & 1], in, q0, q1);
     if (b > 0) c.h2d += b;
     return b < 0 ? -1 : 0;
   };
+  if (in.cat) {  // once per call, ahead of the first window's copies on their stream
+    const int64_t b = upload_catalogs(d, in.cat);
+    if (b < 0) return -1;
+    c.h2d += b;
+  }
   if (enqueue(0)) return -1;
   for (int k = 0; k < nwin; ++k) {
     FusedWin& B = d->fw[k & 1];
@@ -1534,11 +1755,11 @@ int run_windows(dp_dlower* d, const dp_wire32* w, FusedCall& c) {
 
 // The problems d->which, left to the host: lowered there while the fused
 // windows solve, then submitted as an ordinary job beside them.
-int submit_host_side(dp_dlower* d, const dp_wire32* w, FusedCall& c) {
+int submit_host_side(dp_dlower* d, const WireIn& in, FusedCall& c) {
   const int32_t nw = (int32_t)d->which.size();
   ResultStage& S = d->s;
   dp_wire sub{};
-  host_subwire(d, w, &sub);
+  host_subwire(d->sub, d->which, in, &sub);
   if (!d->side) d->side = dp_lowered_new();
   if (dp_lower_into(&sub, DP_LOWER_NARROW | DP_LOWER_PACKED | DP_LOWER_PINNED, d->side) != 0)
     return dl_fail("dp_lower: malformed wire batch");
@@ -1617,7 +1838,30 @@ int merge_by_problem(dp_dlower* d, int32_t P) {
   return 0;
 }
 
+int lower_solve_in(dp_dlower* d, const WireIn& in, WireFault fault, dp_solved* out);
+
+// The pair of wires of a shared call: both well-formed, one string table (the
+// same count and index width) and every query's catalog in [-1, B).  *fault
+// is WIRE_ARRAYS when an array either wire's totals call for is missing.
+// Returns 0, or -1 with the text set.
+int check_shared(const dp_wire32* k, const dp_wire32* q, const int32_t* qc, WireFault* fault) {
+  const WireFault fk = check_wire(k), fq = check_wire(q);
+  if (fk == WIRE_OFFSETS || fq == WIRE_OFFSETS) return dl_fail("dp_lower: malformed wire batch");
+  if (k->n_strs != q->n_strs) return dl_fail("dp_lower_solve_shared: the wires' string tables differ");
+  const int32_t B = k->n_problems, P = q->n_problems;
+  if ((k->var_id16 != nullptr) != (q->var_id16 != nullptr))
+    return dl_fail("dp_lower_solve_shared: the wires' index widths differ");
+  for (int32_t p = 0; p < P; ++p)
+    if (qc[p] < -1 || qc[p] >= B) return dl_fail("dp_lower_solve_shared: query_catalog out of range");
+  *fault = fk != WIRE_OK ? fk : fq;
+  return 0;
+}
 }  // namespace
+
+struct dp_expanded {
+  SubStore store;
+  dp_wire wire{};
+};
 
 extern "C" {
 
@@ -1625,6 +1869,52 @@ int dp_lower_solve(dp_dlower* d, const dp_wire32* w, dp_solved* out) {
   if (!d || !w || !out) return dl_fail("dp_lower_solve: null argument");
   const WireFault fault = check_wire(w);
   if (fault == WIRE_OFFSETS) return dl_fail("dp_lower: malformed wire batch");
+  WireIn in;
+  in.w = w;
+  return lower_solve_in(d, in, fault, out);
+}
+
+int dp_lower_solve_shared(dp_dlower* d, const dp_wire32* catalogs, const dp_wire32* queries,
+                          const int32_t* query_catalog, dp_solved* out) {
+  if (!d || !catalogs || !queries || !query_catalog || !out) return dl_fail("dp_lower_solve_shared: null argument");
+  WireFault fault = WIRE_OK;
+  if (check_shared(catalogs, queries, query_catalog, &fault)) return -1;
+  WireIn in;
+  in.w = queries;
+  in.cat = catalogs;
+  in.qc = query_catalog;
+  return lower_solve_in(d, in, fault, out);
+}
+
+dp_expanded* dp_expand_shared(const dp_wire32* catalogs, const dp_wire32* queries, const int32_t* query_catalog) {
+  if (!catalogs || !queries || !query_catalog) {
+    dl_fail("dp_expand_shared: null argument");
+    return nullptr;
+  }
+  WireFault fault = WIRE_OK;
+  if (check_shared(catalogs, queries, query_catalog, &fault)) return nullptr;
+  if (fault != WIRE_OK) {
+    dl_fail("dp_lower: malformed wire batch");
+    return nullptr;
+  }
+  auto* e = new dp_expanded;
+  WireIn in;
+  in.w = queries;
+  in.cat = catalogs;
+  in.qc = query_catalog;
+  std::vector<int32_t> all((size_t)queries->n_problems);
+  for (int32_t p = 0; p < queries->n_problems; ++p) all[(size_t)p] = p;
+  host_subwire(e->store, all, in, &e->wire);
+  return e;
+}
+const dp_wire* dp_expanded_wire(const dp_expanded* e) { return e ? &e->wire : nullptr; }
+void dp_expanded_free(dp_expanded* e) { delete e; }
+
+}  // extern "C"
+
+namespace {
+int lower_solve_in(dp_dlower* d, const WireIn& in, WireFault fault, dp_solved* out) {
+  const dp_wire32* const w = in.w;
   std::lock_guard<std::mutex> lk(d->mu);
   const double t0 = dl_ms();
   FusedCall c;
@@ -1656,18 +1946,18 @@ int dp_lower_solve(dp_dlower* d, const dp_wire32* w, dp_solved* out) {
   // The device path, unless the records would not be the forms the solve
   // reads as they lie: placement overrides stage other forms on the host.
   const int32_t forced = DP_OPT_FORCE_GROUP | DP_OPT_FORCE_HBM | DP_OPT_FORCE_MID | DP_OPT_FORCE_LDSG;
-  const bool on_device = !(dp::ctx_flags(d->ctx) & forced) && dp::ldsg_env() != dp::LDSG_ALWAYS && device_takes(w);
+  const bool on_device = !(dp::ctx_flags(d->ctx) & forced) && dp::ldsg_env() != dp::LDSG_ALWAYS && device_takes(in);
   std::vector<int32_t>& which = d->which;  // the problems left to the host
   which.clear();
   if (on_device) {
-    if (run_windows(d, w, c)) return fail(d, c);
+    if (run_windows(d, in, c)) return fail(d, c);
   } else {
     which.resize((size_t)P);
     for (int32_t p = 0; p < P; ++p) which[(size_t)p] = p;
   }
   const int32_t nw = (int32_t)which.size();
   const double th = dl_ms();
-  if (nw > 0 && submit_host_side(d, w, c)) return fail(d, c);
+  if (nw > 0 && submit_host_side(d, in, c)) return fail(d, c);
   const double tw = dl_ms();
   c.host = tw - th;
   if (settle(d, c)) {
@@ -1703,6 +1993,9 @@ int dp_lower_solve(dp_dlower* d, const dp_wire32* w, dp_solved* out) {
                  P, dl_ms() - t0, c.lower_wait, c.plan, c.host, c.wait, dl_ms() - tmg, nw);
   return 0;
 }
+}  // namespace
+
+extern "C" {
 
 int32_t dp_dlower_error(const dp_dlower* d, int32_t p, const char** msg) {
   if (msg) *msg = "";

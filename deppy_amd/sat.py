@@ -312,22 +312,59 @@ class _Input:
         self.err = None
 
 
-def encode_inputs(inputs: Sequence[Sequence[Variable]]) -> _lib.WireArrays:
-    """[]Variable per problem -> wire arrays (identifiers interned per batch)."""
-    strs: dict = {}
-    str_bytes = bytearray()
-    str_off = [0]
+class _Strings:
+    """A string table under construction: identifier -> index, interned."""
 
-    def sid(x) -> int:
+    def __init__(self):
+        self.strs: dict = {}
+        self.str_bytes = bytearray()
+        self.str_off = [0]
+
+    def sid(self, x) -> int:
         b = str(x).encode("utf-8", "surrogateescape")
-        i = strs.get(b)
+        i = self.strs.get(b)
         if i is None:
-            i = len(str_off) - 1
-            strs[b] = i
-            str_bytes.extend(b)
-            str_off.append(len(str_bytes))
+            i = len(self.str_off) - 1
+            self.strs[b] = i
+            self.str_bytes.extend(b)
+            self.str_off.append(len(self.str_bytes))
         return i
 
+
+def encode_inputs(inputs: Sequence[Sequence[Variable]]) -> _lib.WireArrays:
+    """[]Variable per problem -> wire arrays (identifiers interned per batch)."""
+    table = _Strings()
+    wire = _encode_lists(inputs, table)
+    return _lib.WireArrays(*wire, table.str_off, bytes(table.str_bytes), True)
+
+
+def encode_shared(catalogs: Sequence[Sequence[Variable]], queries: Sequence, pinned: bool = True,
+                  ids16: bool = True):
+    """Shared-catalog input of dp_lower_solve_shared.  catalogs: a []Variable
+    each; queries: (catalog index or None, []Variable) each, the problem
+    being the catalog's variables followed by the query's.  Everything is
+    interned into one string table.  -> (catalogs' Wire32Arrays, queries'
+    Wire32Arrays, query_catalog), the last an int32 array (-1: no catalog)
+    held by the queries' object."""
+    table = _Strings()
+    kw = _encode_lists(catalogs, table)
+    qw = _encode_lists([q for _, q in queries], table)
+    so, sb = list(table.str_off), bytes(table.str_bytes)
+    k32 = _lib.Wire32Arrays(_lib.WireArrays(*kw, so, sb, True), pinned=pinned, ids16=ids16)
+    q32 = _lib.Wire32Arrays(_lib.WireArrays(*qw, so, sb, True), pinned=pinned, ids16=ids16)
+    qc = [-1 if b is None else int(b) for b, _ in queries]
+    if any(b < -1 or b >= len(catalogs) for b in qc):
+        raise ValueError("encode_shared: a query's catalog index is out of range")
+    buf = _lib.HostArray(len(qc), np.int32) if pinned else None
+    arr = buf.a if pinned else np.zeros(len(qc), np.int32)
+    arr[:] = qc
+    q32._bufs["query_catalog"] = buf
+    q32.query_catalog = arr
+    return k32, q32, arr
+
+
+def _encode_lists(inputs, table: _Strings) -> tuple:
+    sid = table.sid
     pvo, vid, vco, ck, cn, cao, ca = [0], [], [0], [], [], [0], []
     for variables in inputs:
         for v in variables:
@@ -341,7 +378,7 @@ def encode_inputs(inputs: Sequence[Sequence[Variable]]) -> _lib.WireArrays:
                 cao.append(len(ca))
             vco.append(vco[-1] + len(cons))
         pvo.append(len(vid))
-    return _lib.WireArrays(pvo, vid, vco, ck, cn, cao, ca, str_off, bytes(str_bytes), True)
+    return pvo, vid, vco, ck, cn, cao, ca
 
 
 class Solver:
@@ -690,6 +727,14 @@ def _solve_batch(inputs, tracer, traced, context, out, fused=False) -> list:
                                   "the tracer sees only its first steps" % (p, TRACE_CAP_MAX),
                                   RuntimeWarning, stacklevel=2)
                 retraced[p] = (rj, jj)
+    return _outcomes(inputs, lw, res, out, w32 is not None, tracer if traced else None, retraced)
+
+
+def _outcomes(inputs, lw, res, out, owners_in_res, tracer=None, retraced=None) -> list:
+    """The reference's outcome of every problem from its lowering and result:
+    (installed | None, error | None).  owners_in_res: a fused solve, whose
+    cores come with their owners."""
+    traced = tracer is not None
     for p in range(len(inputs)):
         variables = inputs[p]
         if lw.err[p] == 1:
@@ -707,7 +752,7 @@ def _solve_batch(inputs, tracer, traced, context, out, fused=False) -> list:
             out[p] = ([variables[v] for v in inst] or None, None)
         elif st == UNSAT:
             applied = []
-            if w32 is not None:
+            if owners_in_res:
                 c0 = int(res["core_off"][p])
                 owners = [(int(res["core_var"][c0 + k]), int(res["core_con"][c0 + k]))
                           for k in range(int(res["core_len"][p]))]
@@ -724,6 +769,38 @@ def _solve_batch(inputs, tracer, traced, context, out, fused=False) -> list:
         else:
             out[p] = (None, InternalError("unexpected internal error"))
     return out
+
+
+def SolveQueries(catalog: Sequence[Variable], queries: Sequence[Sequence[Variable]],
+                 context: Optional[_lib.Context] = None) -> list:
+    """Solve catalog + q for every q of queries, the catalog crossing to the
+    GPU once (dp_lower_solve_shared): exactly what
+    SolveBatch([list(catalog) + list(q) for q in queries], fused=True)
+    returns, variables of the outcome being the catalog's and the query's own
+    objects."""
+    catalog = list(catalog)
+    inputs = [catalog + list(q) for q in queries]
+    out: list = [None] * len(inputs)
+    if not inputs:
+        return out
+    try:
+        k32, q32, qc = encode_shared([catalog], [(0, v[len(catalog):]) for v in inputs])
+    except ValueError:  # does not fit the compact wire: the expanded problems' path
+        return SolveBatch(inputs, context=context, fused=True)
+    _lowering.busy = getattr(_lowering, "busy", 0) + 1
+    try:
+        with (contextlib.nullcontext() if context else _ctx_lock):
+            ctx = context or device_context()
+            if _lowering.busy > 1:  # inside this thread's SolveBatch: storage of its own
+                dl = _lib.DeviceLowerer(ctx)
+                res = {k: (v.copy() if isinstance(v, np.ndarray) else v)
+                       for k, v in dl.lower_solve_shared(k32, q32, qc).items()}
+                dl.close()
+            else:
+                res = _device_lowerer(ctx).lower_solve_shared(k32, q32, qc)
+        return _outcomes(inputs, _FusedLowering(res), res, out, True)
+    finally:
+        _lowering.busy -= 1
 
 
 def _dup_id(variables):

@@ -458,6 +458,39 @@ int dp_lower_solve(dp_dlower* d, const dp_wire32* wire, dp_solved* out);
 /* enum dp_lower_err of problem p of the last dp_lower_solve; *msg (may be
  * NULL) receives the reference's error text. */
 int32_t dp_dlower_error(const dp_dlower* d, int32_t p, const char** msg);
+
+/* Shared-catalog queries: dp_lower_solve on many problems that begin with
+ * the same variables, without sending those once per problem.  Problem p of
+ * the call is the problem whose variables are catalog query_catalog[p]'s in
+ * order followed by query p's own in order (query_catalog[p] == -1: query p
+ * alone, as dp_lower_solve solves it), and every result is what
+ * dp_lower_solve gives on that expanded problem: variable indices (installed
+ * bits, core_var) are the expanded problem's, a query's i-th variable being
+ * number nv_catalog + i.  Replaces one sat.NewSolver(sat.WithInput(catalog +
+ * query variables)) + Solve per query (solve.go:133).  Arguments may name
+ * identifiers of either segment; an identifier in both is a
+ * DuplicateIdentifier; constraints of the two segments share identities as
+ * those of one problem do (lit_mapping.go:69-72).  Catalogs are not solved on
+ * their own.  Both wires index one string table (the same n_strs, both with
+ * 16-bit or both with 32-bit indices).  The catalogs' wire goes to the device
+ * once per call and every window's lowering reads it there; per window only
+ * the queries' ranges and their catalog numbers are copied.  The whole call
+ * fails (-1 and a text, as a malformed wire does) when the string tables or
+ * index widths differ, a query_catalog entry is outside [-1,
+ * catalogs->n_problems), or an offset array is not monotone.  Everything else
+ * -- windows, host-lowered problems, dp_dlower_error, the arrays' lifetime --
+ * as dp_lower_solve; NULL arguments return -1 without touching a device. */
+int dp_lower_solve_shared(dp_dlower* d, const dp_wire32* catalogs, const dp_wire32* queries,
+                          const int32_t* query_catalog /* [queries->n_problems], -1..B-1 */, dp_solved* out);
+/* The expanded problems of such a call as a 64-bit wire batch, made on the
+ * host without a device: what dp_lower_solve_shared is defined against, and what its host
+ * fallback lowers.  The handle owns the wire's arrays; the string table is
+ * the queries' (not copied: it must outlive the handle's use).  NULL on the
+ * errors above (dp_last_global_error()).  No reference counterpart. */
+typedef struct dp_expanded dp_expanded;
+dp_expanded* dp_expand_shared(const dp_wire32* catalogs, const dp_wire32* queries, const int32_t* query_catalog);
+const dp_wire* dp_expanded_wire(const dp_expanded* e);
+void dp_expanded_free(dp_expanded* e);
 /* Page-locked host memory for wire batches (the H2D copy then runs by DMA
  * from where they lie).  NULL without a device. */
 void* dp_host_alloc(int64_t bytes);
