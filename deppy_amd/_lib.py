@@ -100,6 +100,7 @@ EXPORTS = [
     "dp_plan_order", "dp_dlower_new", "dp_dlower_free", "dp_lower_device", "dp_dlower_host_count",
     "dp_host_alloc", "dp_host_free", "dp_lower_solve", "dp_dlower_error", "dp_plan_order_heads",
     "dp_lower_solve_shared", "dp_expand_shared", "dp_expanded_wire", "dp_expanded_free",
+    "dp_lower_solve_traced", "dp_lower_solve_shared_traced", "dp_trace_owners_host",
 ]
 
 
@@ -146,6 +147,12 @@ class Solved(ctypes.Structure):
                 ("steps", c_i64p), ("installed", c_u32p), ("inst_off", c_i64p), ("core_len", c_i32p),
                 ("core_off", c_i64p), ("core", c_i32p), ("core_var", c_i32p), ("core_con", c_i32p),
                 ("h2d_bytes", ctypes.c_int64), ("d2h_bytes", ctypes.c_int64), ("host_lowered", ctypes.c_int64)]
+
+
+class Traced(ctypes.Structure):
+    """dp_traced (include/deppy_hip.h): the search traces of a traced fused
+    call, owned by the dp_dlower like the dp_solved arrays."""
+    _fields_ = [("trace_off", c_i64p), ("trace", c_i32p), ("trace_var", c_i32p), ("trace_con", c_i32p)]
 
 
 class Opts(ctypes.Structure):
@@ -299,6 +306,12 @@ def lib():
         L.dp_expanded_wire.argtypes = [vp]
         L.dp_expanded_wire.restype = ctypes.POINTER(Wire)
         L.dp_expanded_free.argtypes = [vp]
+    if hasattr(L, "dp_lower_solve_traced"):
+        L.dp_lower_solve_traced.argtypes = [vp, ctypes.POINTER(Wire32), ctypes.c_int32, ctypes.POINTER(Solved),
+                                            ctypes.POINTER(Traced)]
+        L.dp_lower_solve_shared_traced.argtypes = [vp, ctypes.POINTER(Wire32), ctypes.POINTER(Wire32), c_i32p,
+                                                   ctypes.c_int32, ctypes.POINTER(Solved), ctypes.POINTER(Traced)]
+        L.dp_trace_owners_host.argtypes = [c_i32p, ctypes.c_int32, ctypes.c_int32, c_i32p, c_i32p, c_i32p, c_i32p]
     L.dp_plan_order_heads.argtypes = [c_i32p, c_i64p, ctypes.c_int32, ctypes.c_int32, c_i32p, c_i32p]
     L.dp_host_alloc.argtypes = [ctypes.c_int64]
     L.dp_host_alloc.restype = vp
@@ -649,32 +662,49 @@ class DeviceLowerer:
         lw._fetch()
         return lw
 
-    def lower_solve(self, w32: Wire32Arrays) -> dict:
+    def lower_solve(self, w32: Wire32Arrays, trace_cap: int = 0) -> dict:
         """dp_lower_solve: the compact wire lowered and solved with the
         records left on the device.  -> views of the dp_solved arrays (valid
         until this object's next call) plus msg (the error text of every
-        problem with err != 0), h2d_bytes, d2h_bytes and host_lowered."""
+        problem with err != 0), h2d_bytes, d2h_bytes and host_lowered.
+        trace_cap > 0 (dp_lower_solve_traced) also records the search trace,
+        trace_cap words reserved per problem: the dict then holds trace_off
+        [P+1], trace (problem p's event records at trace_off[p] ..
+        trace_off[p+1]) and trace_var / trace_con (the owner of every
+        identity word, -1 elsewhere); fused_trace_events decodes them."""
         L = lib()
         ws = w32.struct()
         so = Solved()
+        if trace_cap > 0:
+            tr = Traced()
+            if L.dp_lower_solve_traced(self.h, ctypes.byref(ws), trace_cap, ctypes.byref(so), ctypes.byref(tr)) != 0:
+                raise ValueError(L.dp_last_global_error().decode())
+            return self._solved(so, tr)
         if L.dp_lower_solve(self.h, ctypes.byref(ws), ctypes.byref(so)) != 0:
             raise ValueError(L.dp_last_global_error().decode())
         return self._solved(so)
 
-    def lower_solve_shared(self, catalogs32: Wire32Arrays, queries32: Wire32Arrays, query_catalog) -> dict:
+    def lower_solve_shared(self, catalogs32: Wire32Arrays, queries32: Wire32Arrays, query_catalog,
+                           trace_cap: int = 0) -> dict:
         """dp_lower_solve_shared: problem p is catalog query_catalog[p]'s
         variables followed by query p's (-1: the query alone); the catalogs
         cross PCIe once per call.  -> as lower_solve, on the expanded
-        problems."""
+        problems (trace_cap > 0: dp_lower_solve_shared_traced)."""
         L = lib()
         qc = _query_catalog(queries32, query_catalog)
         ks, qs = catalogs32.struct(), queries32.struct()
         so = Solved()
+        if trace_cap > 0:
+            tr = Traced()
+            if L.dp_lower_solve_shared_traced(self.h, ctypes.byref(ks), ctypes.byref(qs), _p(qc, c_i32p), trace_cap,
+                                              ctypes.byref(so), ctypes.byref(tr)) != 0:
+                raise ValueError(L.dp_last_global_error().decode())
+            return self._solved(so, tr)
         if L.dp_lower_solve_shared(self.h, ctypes.byref(ks), ctypes.byref(qs), _p(qc, c_i32p), ctypes.byref(so)) != 0:
             raise ValueError(L.dp_last_global_error().decode())
         return self._solved(so)
 
-    def _solved(self, so: Solved) -> dict:
+    def _solved(self, so: Solved, tr: "Traced | None" = None) -> dict:
         L = lib()
         n = so.n_problems
         out = dict(err=_view(self, so.err, n, ctypes.c_int32, np.int32),
@@ -695,6 +725,11 @@ class DeviceLowerer:
             msg[p] = m.value.decode("utf-8", "surrogateescape")
         out.update(msg=msg, h2d_bytes=int(so.h2d_bytes), d2h_bytes=int(so.d2h_bytes),
                    host_lowered=int(so.host_lowered))
+        if tr is not None:
+            out["trace_off"] = _view(self, tr.trace_off, n + 1, ctypes.c_int64, np.int64)
+            nt = int(out["trace_off"][-1])
+            for k in ("trace", "trace_var", "trace_con"):
+                out[k] = _view(self, getattr(tr, k), nt, ctypes.c_int32, np.int32)
         return out
 
     @property
@@ -1054,6 +1089,29 @@ def trace_events(res: dict, p: int) -> list:
         m = int(t[i])
         ev.append((vs, [int(x) for x in t[i + 1:i + 1 + m]]))
         i += 1 + m
+    return ev
+
+
+def fused_trace_events(res: dict, p: int) -> list:
+    """The search-trace events of problem p of a traced fused solve
+    (DeviceLowerer.lower_solve(..., trace_cap)): [(guessed variables,
+    [(owner variable, index in its Constraints()) of every identity])].  A
+    malformed stream (a negative count, an event past the end) ends the list
+    at the last whole event."""
+    t0, t1 = int(res["trace_off"][p]), int(res["trace_off"][p + 1])
+    t = res["trace"][t0:t1]
+    tv, tc = res["trace_var"][t0:t1], res["trace_con"][t0:t1]
+    ev, i, end = [], 0, len(t)
+    while i < end:
+        n = int(t[i])
+        if n < 0 or i + 1 + n >= end:
+            break
+        m = int(t[i + 1 + n])
+        j = i + 2 + n
+        if m < 0 or j + m > end:
+            break
+        ev.append(([int(x) for x in t[i + 1:i + 1 + n]], [(int(tv[k]), int(tc[k])) for k in range(j, j + m)]))
+        i = j + m
     return ev
 
 

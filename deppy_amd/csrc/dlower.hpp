@@ -33,6 +33,12 @@ struct FusedSrc {
   const int32_t *dev_nid, *dev_ivs, *dev_ics;
   int32_t owner_stride;
   int32_t *core_var, *core_con;  // host: owners of res->core, indexed as it is
+  // A traced job (dp_lower_solve_traced): problem i's search trace goes to
+  // dev_trace + i * trace_cap and its length to dev_trace_len[i], both device
+  // memory.  Untraced: null, null and 0.
+  int32_t* dev_trace;
+  int32_t* dev_trace_len;
+  int32_t trace_cap;
 };
 // dp_submit with byte accounting: *h2d / *d2h (may be null) grow by every
 // byte the job's chunks move over PCIe (kernel writes to and reads from

@@ -104,6 +104,16 @@ hipError_t launch_watch_build(const KernelArgs& a, int mode, int n_items, hipStr
 hipError_t launch_core_owners(const WorkItem* items, int n_items, const ProblemOut* out, const int32_t* core,
                               int64_t core_cap, int32_t* own_var, int32_t* own_con, const int32_t* nid,
                               const int32_t* ivs, const int32_t* ics, int32_t stride, hipStream_t stream);
+// After a traced fused window's job (trace_owners.hip): the n problems'
+// traces -- problem p's trace_len[p] words at region + p * trace_cap --
+// written densely to out + trace_off[p], with the owner of every identity
+// word (ivs / ics[p * stride + id], -1 outside [0, nid[p])) at the same
+// position of out_var / out_con and -1 at every other word.  out* hold
+// out_words words; a range past them is not written.
+hipError_t launch_trace_pack(int32_t n, const int32_t* region, const int32_t* trace_len, int32_t trace_cap,
+                             const int64_t* trace_off, const int32_t* nid, const int32_t* ivs, const int32_t* ics,
+                             int32_t stride, int64_t out_words, int32_t* out, int32_t* out_var, int32_t* out_con,
+                             hipStream_t stream);
 // Raise the kernel's dynamic-LDS limit to the device maximum.
 hipError_t configure_solve_kernel(int max_lds_bytes);
 

@@ -38,6 +38,14 @@
 // the windows copy only the queries', and the kernel's shared instantiation
 // reads a problem's first variables, constraints and arguments from its
 // catalog and the rest from the query.
+//
+// dp_lower_solve_traced / dp_lower_solve_shared_traced are the two calls with
+// the search trace (WithTracer, solve.go:141-146; Tracer.Trace,
+// search.go:173): each window's solve writes its traces into a device region
+// of the window's, and once the window's job is done a kernel packs the
+// words that were written into page-locked memory with the owner of every
+// identity word beside it (trace_owners.hip), so a trace costs 12 bytes a
+// word over PCIe and the owners never leave the device as a whole.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -52,9 +60,11 @@
 #include "common.hpp"
 #include "dlower.hpp"
 #include "hostmem.hpp"
+#include "kernel_api.hpp"
 #include "layout.hpp"
 #include "placement.hpp"
 #include "pool.hpp"
+#include "trace_walk.hpp"
 
 namespace {
 
@@ -982,8 +992,58 @@ struct FusedWin {
   dp_job* job = nullptr;
   int64_t job_h2d = 0, job_d2h = 0;  // the job's PCIe bytes (its own counters: jobs run side by side)
   int32_t q0 = 0, n = 0;
+  // a traced call (dp_lower_solve_traced): the window's trace region, n *
+  // trace_cap words, and the lengths; to_pack from the job's submission until
+  // its traces are packed (pack_window)
+  DevBuf<int32_t> trace, tlen;
+  bool to_pack = false;
   ~FusedWin() {
     if (lowered) (void)hipEventDestroy(lowered);
+  }
+};
+
+// Mapped page-locked memory that grows keeping what it holds (the packed
+// traces: a call's total is known only window by window).
+template <class T>
+struct MapKeep {
+  T *h = nullptr, *d = nullptr;
+  size_t cap = 0;
+  bool need(size_t n, size_t keep) {
+    if (n <= cap && h) return true;
+    const size_t c = std::max<size_t>(std::max(n, 2 * cap), 1024);
+    T *nh = nullptr, *nd = nullptr;
+    hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&nh), c * sizeof(T), hipHostMallocPortable | hipHostMallocMapped);
+    if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void**>(&nd), nh, 0);
+    if (e != hipSuccess) {
+      if (nh) (void)hipHostFree(nh);
+      (void)hipGetLastError();
+      return false;
+    }
+    if (h) {
+      std::memcpy(nh, h, std::min(keep, cap) * sizeof(T));
+      (void)hipHostFree(h);
+    }
+    h = nh;
+    d = nd;
+    cap = c;
+    return true;
+  }
+  ~MapKeep() {
+    if (h) (void)hipHostFree(h);
+  }
+};
+
+// A call's traces in one layout: problem p's words at [off[p], off[p+1]) of
+// words, each word's owner at the same position of var / con.
+struct TraceSet {
+  MapKeep<int64_t> off;
+  MapKeep<int32_t> words, var, con;
+  bool need_words(size_t n, size_t keep) { return words.need(n, keep) && var.need(n, keep) && con.need(n, keep); }
+  void publish(dp_traced* t) const {
+    t->trace_off = off.h;
+    t->trace = words.h;
+    t->trace_var = var.h;
+    t->trace_con = con.h;
   }
 };
 
@@ -1060,6 +1120,7 @@ struct SubStore {
 };
 
 constexpr int32_t kFusedWindow = 16384;  // problems per window: 320 MiB of slots and owners at most
+constexpr int32_t kTraceCapMax = 1 << 24;  // the largest trace reservation per problem anything asks for
 
 }  // namespace
 
@@ -1080,6 +1141,14 @@ struct dp_dlower {
   dp_lowered* side = nullptr;   // the host-lowered problems' records
   std::vector<int32_t> f_which;  // the problems of the last dp_lower_solve lowered on the host (ascending)
   std::vector<int32_t> f_err;    // their enum dp_lower_err
+  // -- dp_lower_solve_traced: the call's reservation (0: untraced), the
+  // windows' traces as the pack kernel writes them, the host-lowered
+  // problems' (dense, with their owners), and the two merged by problem index
+  int32_t t_cap = 0;
+  TraceSet tv, tm;
+  PinBuf<int32_t> h_tlen;  // a window's lengths
+  std::vector<int32_t> s_region, s_tlen, s_words, s_var, s_con;
+  std::vector<int64_t> s_toff;
   hipStream_t st = nullptr;   // kernels and the copies back
   hipStream_t cst = nullptr;  // the wire's copies to the device
   hipStream_t pst = nullptr;  // the packing (its writes to host memory run under the next piece's lowering)
@@ -1612,6 +1681,11 @@ int64_t enqueue_window(dp_dlower* d, FusedWin& B, const WireIn& w, int32_t q0, i
   B.n = n;
   DL_OK(B.heads.need((size_t)n * DP_H_SIZE));
   DL_OK(B.counts.need((size_t)n * 2));
+  if (d->t_cap > 0) {  // (the buffer's last job has been waited for and packed)
+    DL_OK(B.trace.need((size_t)n * (size_t)d->t_cap));
+    DL_OK(B.tlen.need((size_t)n));
+    DL_OK(hipMemsetAsync(B.tlen.p, 0, (size_t)n * 4, d->st));  // (new storage; the chunk zeroes it again)
+  }
   const int64_t bytes = B.wire.enqueue(d, w, q0, q1, [](int32_t, int32_t) { return hipSuccess; });
   if (bytes < 0) return -1;
   hipLaunchKernelGGL(heads_kernel, dim3((unsigned)(((int64_t)n * DP_H_SIZE + HEADS_T - 1) / HEADS_T)), dim3(HEADS_T),
@@ -1627,6 +1701,16 @@ int32_t fused_window() {  // (read per call)
   return v > 0 ? (int32_t)std::min<long long>(v, kFusedWindow) : kFusedWindow;
 }
 
+// A traced call's bound on one window buffer's trace region, and on a piece
+// of the host-lowered problems: 256 MiB, a full window at 4,096 words a
+// problem (DEPPY_FUSED_TRACE_BYTES, read per call).  -> problems, at least 1.
+int32_t traced_problems(int32_t trace_cap) {
+  const char* e = std::getenv("DEPPY_FUSED_TRACE_BYTES");
+  const long long v = e && *e ? std::atoll(e) : 0;
+  const long long bytes = v > 0 ? v : 256ll << 20;
+  return (int32_t)std::min<long long>(std::max<long long>(1, bytes / (4ll * trace_cap)), kFusedWindow);
+}
+
 // Wait for B's job, if it has one, and take its PCIe bytes.
 int wait_window(dp_dlower* d, FusedWin& B, FusedCall& c) {
   if (!B.job) return 0;
@@ -1635,6 +1719,32 @@ int wait_window(dp_dlower* d, FusedWin& B, FusedCall& c) {
   c.h2d += B.job_h2d;
   c.d2h += B.job_d2h;
   return rc ? -1 : 0;
+}
+
+// A traced window whose job has been waited for: its lengths come back (4
+// bytes a problem), the host extends the call's offsets by them, and the
+// pack kernel writes the words that were written, with their owners,
+// straight into the page-locked output (trace_owners.hip).  Windows are
+// packed in problem order; the call waits for the kernel, so the buffer is
+// free to be lowered into again.
+int pack_window(dp_dlower* d, FusedWin& B, FusedCall& c) {
+  if (!B.to_pack) return 0;
+  B.to_pack = false;
+  const int32_t n = B.n, cap = d->t_cap;
+  TraceSet& T = d->tv;
+  if (!d->h_tlen.need((size_t)n)) return dl_fail("dp_lower_solve: page-locked allocation failed");
+  DL_OK(hipMemcpyAsync(d->h_tlen.p, B.tlen.p, (size_t)n * 4, hipMemcpyDeviceToHost, d->pst));
+  DL_OK(hipStreamSynchronize(d->pst));
+  int64_t* off = T.off.h + B.q0;  // (off[0]: the windows' before this one)
+  for (int32_t i = 0; i < n; ++i) off[i + 1] = off[i] + std::min(std::max(d->h_tlen.p[i], 0), cap);
+  if (!T.need_words((size_t)off[n] + 1, (size_t)off[0]))
+    return dl_fail("dp_lower_solve: page-locked allocation failed");
+  DL_OK(dp::launch_trace_pack(n, B.trace.p, B.tlen.p, cap, T.off.d + B.q0, B.wire.nid.p, B.wire.ivs.p, B.wire.ics.p,
+                              DL_C, (int64_t)T.words.cap, T.words.d, T.var.d, T.con.d, d->pst));
+  DL_OK(hipStreamSynchronize(d->pst));
+  c.d2h += (int64_t)n * 4 + 12 * (off[n] - off[0]);
+  c.h2d += ((int64_t)n + 1) * 8;  // (the offsets the kernel reads from host memory)
+  return 0;
 }
 
 // Every job still in flight is waited for: the windows', then the
@@ -1658,6 +1768,7 @@ int fail(dp_dlower* d, FusedCall& c) {
   const std::string keep = dp_last_global_error();
   drain(d);
   (void)settle(d, c);
+  for (auto& B : d->fw) B.to_pack = false;
   d->v.core.wipe();
   d->s.core.wipe();
   d->m.core.wipe();
@@ -1690,11 +1801,17 @@ int submit_window(dp_dlower* d, FusedWin& B, int64_t inst_cap, int64_t core_cap)
   F.owner_stride = DL_C;
   F.core_var = V.core.cvar.p;
   F.core_con = V.core.ccon.p;
+  if (d->t_cap > 0) {
+    F.dev_trace = B.trace.p;
+    F.dev_trace_len = B.tlen.p;
+    F.trace_cap = d->t_cap;
+  }
   dp_batch fb{B.n, d->f_rec_off.data(), nullptr};
   dp_result fr = V.at(B.q0);
   B.job_h2d = B.job_d2h = 0;
   if (dp::submit_job(d->ctx, &fb, &fr, &F, &B.job_h2d, &B.job_d2h, &B.job) != 0)
     return dl_fail("dp_lower_solve: the solve could not be submitted");
+  B.to_pack = d->t_cap > 0;
   return 0;
 }
 
@@ -1706,7 +1823,8 @@ int run_windows(dp_dlower* d, const WireIn& in, FusedCall& c) {
   if (hipSetDevice(d->dev) != hipSuccess) return dl_fail("dp_lower_solve: hipSetDevice failed");
   const int32_t P = in.w->n_problems;
   const int32_t W = fused_window();
-  const int32_t win = P <= W ? P : std::max<int32_t>(1, W / 2);
+  int32_t win = P <= W ? P : std::max<int32_t>(1, W / 2);
+  if (d->t_cap > 0) win = std::min(win, traced_problems(d->t_cap));  // one buffer's trace region
   const int32_t nwin = (P + win - 1) / win;
   // staging of the windows' results, sized from the wire's totals (a bitmap
   // word per 32 variables, an identity per constraint at most)
@@ -1748,6 +1866,7 @@ int run_windows(dp_dlower* d, const WireIn& in, FusedCall& c) {
     const int rc = wait_window(d, d->fw[(k + 1) & 1], c);
     c.wait += dl_ms() - tw;
     if (rc) return dl_fail(dp_last_error(d->ctx));
+    if (pack_window(d, d->fw[(k + 1) & 1], c)) return -1;  // its traces, before the buffer is lowered into
     if (enqueue(k + 1)) return -1;
   }
   return 0;
@@ -1769,9 +1888,43 @@ int submit_host_side(dp_dlower* d, const WireIn& in, FusedCall& c) {
     return dl_fail("dp_lower_solve: page-locked allocation failed");
   d->f_err.assign((size_t)nw, 0);
   (void)dp_lowered_errors(d->side, d->f_err.data());
+  if (d->t_cap > 0) return 0;  // traced: solve_host_side_traced, once the windows are done
   dp_result sr = S.at(0);
   if (dp::submit_job(d->ctx, &sb, &sr, nullptr, &c.side_h2d, &c.side_d2h, &c.side_job) != 0)
     return dl_fail("dp_lower_solve: the solve could not be submitted");
+  return 0;
+}
+
+// A traced call's host-lowered problems: the pipeline does not trace, so
+// they are solved through the traced resident form (dp_solve_traced), in
+// pieces whose trace regions stay within the windows' bound, and each
+// piece's traces are kept densely (d->s_words at d->s_toff).
+int solve_host_side_traced(dp_dlower* d, FusedCall& c) {
+  const int32_t nw = (int32_t)d->which.size(), cap = d->t_cap;
+  ResultStage& S = d->s;
+  const int64_t* ro = dp_lowered_rec_off(d->side);
+  const int32_t piece = std::min(nw, traced_problems(cap));
+  d->s_region.resize((size_t)piece * (size_t)cap);
+  d->s_tlen.assign((size_t)nw, 0);
+  d->s_toff.assign((size_t)nw + 1, 0);
+  d->s_words.clear();
+  for (int32_t j0 = 0; j0 < nw; j0 += piece) {
+    const int32_t n = std::min(piece, nw - j0);
+    dp_batch pb{n, ro + j0, dp_lowered_rec(d->side)};
+    dp_result pr = S.at(j0);
+    if (dp_solve_traced(d->ctx, &pb, cap, &pr, d->s_region.data(), d->s_tlen.data() + j0) != 0)
+      return dl_fail(dp_last_error(d->ctx));
+    for (int32_t i = 0; i < n; ++i) {
+      const int32_t len = std::min(std::max(d->s_tlen[(size_t)(j0 + i)], 0), cap);
+      const int32_t* t = d->s_region.data() + (size_t)i * (size_t)cap;
+      d->s_words.insert(d->s_words.end(), t, t + len);
+      d->s_toff[(size_t)(j0 + i) + 1] = d->s_toff[(size_t)(j0 + i)] + len;
+    }
+    // the records up; the results, the lengths and the whole regions back
+    c.h2d += 4 * (ro[j0 + n] - ro[j0]);
+    c.d2h += (int64_t)n * (17 + 4 + 4 * (int64_t)cap) + 4 * (S.inst_off.p[j0 + n] - S.inst_off.p[j0]) +
+             4 * (S.core_off.p[j0 + n] - S.core_off.p[j0]);
+  }
   return 0;
 }
 
@@ -1794,6 +1947,16 @@ void map_host_side(dp_dlower* d) {
       S.core.ccon.p[at + k] = ok ? ic[io[j] + id] : -1;
     }
     S.core.dirty.emplace_back(at, len);
+  }
+  if (d->t_cap > 0) {  // and their traces' owners: the device's walk, on the host
+    d->s_var.resize(d->s_words.size());
+    d->s_con.resize(d->s_words.size());
+    for (int32_t j = 0; j < nw; ++j) {
+      const int64_t t0 = d->s_toff[(size_t)j];
+      const int64_t nid = std::min<int64_t>(io[j + 1] - io[j], INT32_MAX);
+      dp::trace_owners_walk(d->s_words.data() + t0, (int32_t)(d->s_toff[(size_t)j + 1] - t0), (int32_t)nid, iv + io[j],
+                            ic + io[j], d->s_var.data() + t0, d->s_con.data() + t0, 0, 1);
+    }
   }
   for (int32_t j = 0; j < nw; ++j) {
     const int32_t p = d->which[(size_t)j];
@@ -1838,7 +2001,35 @@ int merge_by_problem(dp_dlower* d, int32_t P) {
   return 0;
 }
 
-int lower_solve_in(dp_dlower* d, const WireIn& in, WireFault fault, dp_solved* out);
+// The windows' traces and the host side's merged by problem index into d->tm
+// (windows: whether any ran; without them every problem is the host's).
+int merge_traces(dp_dlower* d, int32_t P, bool windows) {
+  const int32_t nw = (int32_t)d->which.size();
+  TraceSet &V = d->tv, &M = d->tm;
+  if (!M.off.need((size_t)P + 1, 0)) return dl_fail("dp_lower_solve: page-locked allocation failed");
+  int64_t* mo = M.off.h;
+  mo[0] = 0;
+  for (int32_t p = 0, j = 0; p < P; ++p) {
+    const bool host = j < nw && d->which[(size_t)j] == p;
+    mo[p + 1] = mo[p] + (host ? d->s_toff[(size_t)j + 1] - d->s_toff[(size_t)j] : windows ? V.off.h[p + 1] - V.off.h[p] : 0);
+    j += host;
+  }
+  if (!M.need_words((size_t)mo[P] + 1, 0)) return dl_fail("dp_lower_solve: page-locked allocation failed");
+  for (int32_t p = 0, j = 0; p < P; ++p) {
+    const bool host = j < nw && d->which[(size_t)j] == p;
+    const size_t len = (size_t)(mo[p + 1] - mo[p]) * 4;
+    if (len) {
+      const int64_t at = host ? d->s_toff[(size_t)j] : V.off.h[p];
+      std::memcpy(M.words.h + mo[p], (host ? d->s_words.data() : V.words.h) + at, len);
+      std::memcpy(M.var.h + mo[p], (host ? d->s_var.data() : V.var.h) + at, len);
+      std::memcpy(M.con.h + mo[p], (host ? d->s_con.data() : V.con.h) + at, len);
+    }
+    j += host;
+  }
+  return 0;
+}
+
+int lower_solve_in(dp_dlower* d, const WireIn& in, WireFault fault, int32_t trace_cap, dp_solved* out, dp_traced* tout);
 
 // The pair of wires of a shared call: both well-formed, one string table (the
 // same count and index width) and every query's catalog in [-1, B).  *fault
@@ -1871,7 +2062,7 @@ int dp_lower_solve(dp_dlower* d, const dp_wire32* w, dp_solved* out) {
   if (fault == WIRE_OFFSETS) return dl_fail("dp_lower: malformed wire batch");
   WireIn in;
   in.w = w;
-  return lower_solve_in(d, in, fault, out);
+  return lower_solve_in(d, in, fault, 0, out, nullptr);
 }
 
 int dp_lower_solve_shared(dp_dlower* d, const dp_wire32* catalogs, const dp_wire32* queries,
@@ -1883,7 +2074,32 @@ int dp_lower_solve_shared(dp_dlower* d, const dp_wire32* catalogs, const dp_wire
   in.w = queries;
   in.cat = catalogs;
   in.qc = query_catalog;
-  return lower_solve_in(d, in, fault, out);
+  return lower_solve_in(d, in, fault, 0, out, nullptr);
+}
+
+int dp_lower_solve_traced(dp_dlower* d, const dp_wire32* w, int32_t trace_cap, dp_solved* out, dp_traced* traced) {
+  if (trace_cap < 1 || trace_cap > kTraceCapMax) return dl_fail("dp_lower_solve_traced: trace_cap outside 1 .. 1<<24");
+  if (!d || !w || !out || !traced) return dl_fail("dp_lower_solve_traced: null argument");
+  const WireFault fault = check_wire(w);
+  if (fault == WIRE_OFFSETS) return dl_fail("dp_lower: malformed wire batch");
+  WireIn in;
+  in.w = w;
+  return lower_solve_in(d, in, fault, trace_cap, out, traced);
+}
+
+int dp_lower_solve_shared_traced(dp_dlower* d, const dp_wire32* catalogs, const dp_wire32* queries,
+                                 const int32_t* query_catalog, int32_t trace_cap, dp_solved* out, dp_traced* traced) {
+  if (trace_cap < 1 || trace_cap > kTraceCapMax)
+    return dl_fail("dp_lower_solve_shared_traced: trace_cap outside 1 .. 1<<24");
+  if (!d || !catalogs || !queries || !query_catalog || !out || !traced)
+    return dl_fail("dp_lower_solve_shared_traced: null argument");
+  WireFault fault = WIRE_OK;
+  if (check_shared(catalogs, queries, query_catalog, &fault)) return -1;
+  WireIn in;
+  in.w = queries;
+  in.cat = catalogs;
+  in.qc = query_catalog;
+  return lower_solve_in(d, in, fault, trace_cap, out, traced);
 }
 
 dp_expanded* dp_expand_shared(const dp_wire32* catalogs, const dp_wire32* queries, const int32_t* query_catalog) {
@@ -1913,7 +2129,8 @@ void dp_expanded_free(dp_expanded* e) { delete e; }
 }  // extern "C"
 
 namespace {
-int lower_solve_in(dp_dlower* d, const WireIn& in, WireFault fault, dp_solved* out) {
+int lower_solve_in(dp_dlower* d, const WireIn& in, WireFault fault, int32_t trace_cap, dp_solved* out,
+                   dp_traced* tout) {
   const dp_wire32* const w = in.w;
   std::lock_guard<std::mutex> lk(d->mu);
   const double t0 = dl_ms();
@@ -1921,6 +2138,16 @@ int lower_solve_in(dp_dlower* d, const WireIn& in, WireFault fault, dp_solved* o
   const int32_t P = w->n_problems;
   ResultStage& V = d->v;
   *out = dp_solved{};
+  const bool traced = tout != nullptr;
+  d->t_cap = traced ? trace_cap : 0;
+  if (traced) {
+    *tout = dp_traced{};
+    // the windows' offsets and a first word of each array (an empty batch
+    // still publishes arrays)
+    if (!d->tv.off.need((size_t)P + 1, 0) || !d->tv.need_words(1, 0))
+      return dl_fail("dp_lower_solve: page-locked allocation failed");
+    d->tv.off.h[0] = 0;
+  }
   d->f_which.clear();
   d->f_err.clear();
   d->host_count = 0;
@@ -1940,6 +2167,7 @@ int lower_solve_in(dp_dlower* d, const WireIn& in, WireFault fault, dp_solved* o
   if (P == 0) {
     if (!V.need_data(0, 0)) return dl_fail("dp_lower_solve: page-locked allocation failed");
     V.publish(out);
+    if (traced) d->tv.publish(tout);
     return 0;
   }
   if (fault != WIRE_OK) return dl_fail("dp_lower: malformed wire batch");
@@ -1964,6 +2192,14 @@ int lower_solve_in(dp_dlower* d, const WireIn& in, WireFault fault, dp_solved* o
     dp::set_global_error(dp_last_error(d->ctx));
     return fail(d, c);
   }
+  if (traced) {
+    // the last windows' traces, in problem order; then the host side's
+    FusedWin* last[2] = {&d->fw[0], &d->fw[1]};
+    if (last[1]->q0 < last[0]->q0) std::swap(last[0], last[1]);
+    for (FusedWin* B : last)
+      if (pack_window(d, *B, c)) return fail(d, c);
+    if (nw > 0 && solve_host_side_traced(d, c)) return fail(d, c);
+  }
   const double tmg = dl_ms();
   c.wait += tmg - tw;
   // the reported cores of the fused windows (their ranges are zeroed again by the next call)
@@ -1981,6 +2217,10 @@ int lower_solve_in(dp_dlower* d, const WireIn& in, WireFault fault, dp_solved* o
     }
   }
   res->publish(out);
+  if (traced) {
+    if (nw > 0 && merge_traces(d, P, on_device)) return fail(d, c);
+    (nw > 0 ? d->tm : d->tv).publish(tout);
+  }
   d->f_which = which;
   d->host_count = nw;
   out->h2d_bytes = c.h2d;

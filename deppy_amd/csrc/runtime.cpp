@@ -235,10 +235,24 @@ struct Plan {
   std::vector<int32_t> big[5], cnt, tmp, grp;
 };
 
+// The staged copy's words (layout.hpp staged_words), and never fewer than a
+// packed record copied as it lies takes: a tiny DP_FMT_P16 record's lengths
+// start at a 16-byte boundary, past where its 16-bit form would end, and
+// stage_one's copy of it ran a word into the next record's header (which the
+// kernel then reported DP_F_MALFORMED).
+int64_t staged_sw(const int32_t* h, bool narrow) {
+  const int64_t w = staged_words(h, narrow);
+  // (only a record of a handful of variables can be short: the 16-bit form
+  // spends a byte more per variable, row and list than the packed one, and 8
+  // on its offsets' last entries, against at most 14 bytes of padding)
+  if (!narrow || h[DP_H_NV] >= 16 || !dp_fmt_packed(h[DP_H_FMT])) return w;
+  return std::max(w, (dp_rec_phys_words(h) + 3) & ~(int64_t)3);
+}
+
 // A mid-size record moved onto M_LDSG: staged (or copied) in 16-bit form.
 void place_ldsg(Head& H, const int32_t* h, bool aligned) {
   H.lds = layout<M_LDSG>(h).lds_bytes;
-  H.sw = staged_words(h, true);
+  H.sw = staged_sw(h, true);
   H.rec_bytes = dp_fmt_packed(h[DP_H_FMT]) ? 4 * dp_rec_phys_words(h)
                                            : 4 * DP_H_SIZE + 2 * ((int64_t)h[DP_H_WORDS] - DP_H_SIZE);
   H.place = M_LDSG;
@@ -271,7 +285,7 @@ void read_head(Head& H, const int32_t* h, int64_t avail, int32_t opt_flags, bool
       H.ldsg_ok = true;
     }
   }
-  H.sw = staged_words(h, nar);
+  H.sw = staged_sw(h, nar);
   // algorithmic input bytes (roofline.achieved): the record as the kernel
   // reads it -- the packed form as it is, else the 16-bit form (LDS path) or
   // the int32 form.  Watch lists are derived data and not counted, whether
@@ -1737,6 +1751,15 @@ int enqueue_fused_chunk(dp_ctx* ctx, Device& D, Lane& L, dp_job* job, int32_t p0
                                  ctx->budget);
   a.rec = F.dev_rec;
   a.core_pool_len = at<int32_t>(L.d_in.p, il.pool_len);  // (zeroed by the copy above)
+  if (F.dev_trace && F.dev_trace_len && F.trace_cap > 0) {
+    // traced: the lengths zeroed ahead of the launches (a problem that is not
+    // launched writes none, as on the resident path, build_slice); the trace
+    // stays in device memory, so the chunk's PCIe bytes are what they were
+    HIP_OK(hipMemsetAsync(F.dev_trace_len + p0, 0, (size_t)n * 4, L.s));
+    a.trace = F.dev_trace + (int64_t)p0 * F.trace_cap;
+    a.trace_len = F.dev_trace_len + p0;
+    a.trace_cap = F.trace_cap;
+  }
   HIP_OK(hipEventRecord(L.k0, L.s));
   set_siblings(D, (int)(&L - D.lanes) % D.nstreams, L.spread, ctx->spread);
   if (enqueue_launches(ctx, P, a, L.s, st, &L.spread)) return -1;

@@ -481,6 +481,17 @@ def _replay_trace(tracer: Tracer, variables: list, lw, p: int, res: dict, j: int
         tracer.Trace(_Position([variables[v] for v in vs], conflicts))
 
 
+def _replay_fused(tracer: Tracer, variables: list, res: dict, p: int) -> None:
+    """_replay_trace from a traced fused solve, whose identity words come
+    with their owners (dp_lower_solve_traced)."""
+    for vs, owners in _lib.fused_trace_events(res, p):
+        conflicts = []
+        for vi, ci in owners:
+            var = variables[vi]
+            conflicts.append(AppliedConstraint(var, var.Constraints()[ci]))
+        tracer.Trace(_Position([variables[v] for v in vs], conflicts))
+
+
 # Lowering storage reused by solve_wire, per calling thread: the records of
 # the last batch (page-locked, packed) stay valid until that thread's next
 # call.  The page-locked storage stays pinned at the size of the thread's
@@ -588,20 +599,23 @@ def _device_lowerer(ctx: _lib.Context) -> "_lib.DeviceLowerer":
     return dl
 
 
-def solve_wire_fused(w32: "_lib.Wire32Arrays", context: Optional[_lib.Context] = None):
+def solve_wire_fused(w32: "_lib.Wire32Arrays", context: Optional[_lib.Context] = None, trace_cap: int = 0):
     """solve_wire's results from the compact wire with the lowering's records
     and owners left on the device (dp_lower_solve): (lowering, results), where
     results also holds core_var / core_con, the AppliedConstraint of every
     core identity, and the call's PCIe bytes.  The arrays are the device
-    lowering's own: valid until this thread's next fused call on the context."""
+    lowering's own: valid until this thread's next fused call on the context.
+    trace_cap > 0 (dp_lower_solve_traced): the results also hold the search
+    traces with the owner of every identity word."""
     with (contextlib.nullcontext() if context else _ctx_lock):
         ctx = context or device_context()
         if getattr(_lowering, "busy", 0) > 1:  # inside this thread's SolveBatch: storage of its own
             dl = _lib.DeviceLowerer(ctx)
-            res = {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in dl.lower_solve(w32).items()}
+            res = {k: (v.copy() if isinstance(v, np.ndarray) else v)
+                   for k, v in dl.lower_solve(w32, trace_cap).items()}
             dl.close()
         else:
-            res = _device_lowerer(ctx).lower_solve(w32)
+            res = _device_lowerer(ctx).lower_solve(w32, trace_cap)
     return _FusedLowering(res), res
 
 
@@ -674,9 +688,10 @@ def SolveBatch(inputs: Sequence[Sequence[Variable]], tracer: Optional[Tracer] = 
                context: Optional[_lib.Context] = None, fused: bool = False) -> list:
     """Solve many independent problems in one GPU launch.
 
-    fused=True (without a tracer, and when the batch fits the compact 32-bit
-    wire) lowers on the GPU and solves the records where they lie
-    (solve_wire_fused); the results are the same.
+    fused=True (when the batch fits the compact 32-bit wire) lowers on the
+    GPU and solves the records where they lie (solve_wire_fused), with a
+    tracer too (dp_lower_solve_traced); the results and the tracer's events
+    are the same.
 
     With a tracer other than DefaultTracer the GPU records every
     unsatisfiable search step and the steps are replayed through
@@ -690,7 +705,7 @@ def SolveBatch(inputs: Sequence[Sequence[Variable]], tracer: Optional[Tracer] = 
         return out
     _lowering.busy = getattr(_lowering, "busy", 0) + 1
     try:
-        return _solve_batch(inputs, tracer, traced, context, out, fused and not traced)
+        return _solve_batch(inputs, tracer, traced, context, out, fused)
     finally:
         _lowering.busy -= 1
 
@@ -704,30 +719,43 @@ def _solve_batch(inputs, tracer, traced, context, out, fused=False) -> list:
         except ValueError:  # does not fit 32 bits: the 64-bit wire's path
             w32 = None
     if w32 is not None:
-        lw, res = solve_wire_fused(w32, context)
+        lw, res = solve_wire_fused(w32, context, TRACE_CAP if traced else 0)
     else:
         lw, res = solve_wire(wire, context, TRACE_CAP if traced else 0)
-    retraced = {}
-    if traced:
-        with (contextlib.nullcontext() if context else _ctx_lock):
-            ctx = context or device_context()
-            for p in range(len(inputs)):
-                if lw.err[p]:
-                    continue
-                rj, jj, cap = res, p, TRACE_CAP
-                while rj["flags"][jj] & _lib.F_TRACE_TRUNCATED and cap < TRACE_CAP_MAX:
-                    cap *= 16
-                    r1 = np.ascontiguousarray(lw.record(p))
-                    rj, jj = ctx.solve(np.array([0, len(r1)], np.int64), r1, cap), 0
-                if rj["flags"][jj] & _lib.F_TRACE_TRUNCATED:
-                    # the reference's tracer sees every unsatisfiable step
-                    # (search.go:173); this one would miss the steps past the
-                    # largest reservation
-                    warnings.warn("deppy_amd: search trace of problem %d truncated at %d words; "
-                                  "the tracer sees only its first steps" % (p, TRACE_CAP_MAX),
-                                  RuntimeWarning, stacklevel=2)
-                retraced[p] = (rj, jj)
+    retraced = _retrace(inputs, lw, res, context, w32 is not None) if traced else {}
     return _outcomes(inputs, lw, res, out, w32 is not None, tracer if traced else None, retraced)
+
+
+def _retrace(inputs, lw, res, context, fused: bool) -> dict:
+    """Where every problem's trace is replayed from: problem -> (results, its
+    index in them, the lowering that maps their identities and its index in
+    it; None: a fused solve's, whose trace comes with its owners).  A
+    truncated trace is re-solved alone with 16x the reservation, from the
+    problem's record (a fused solve keeps none on the host: the problem is
+    lowered again, on its own)."""
+    retraced = {}
+    with (contextlib.nullcontext() if context else _ctx_lock):
+        ctx = context or device_context()
+        for p in range(len(inputs)):
+            if lw.err[p]:
+                continue
+            rj, jj, cap = res, p, TRACE_CAP
+            lwj, pj = (None, 0) if fused else (lw, p)
+            while rj["flags"][jj] & _lib.F_TRACE_TRUNCATED and cap < TRACE_CAP_MAX:
+                cap *= 16
+                if lwj is None:
+                    lwj, pj = _lib.Lowered(encode_inputs([inputs[p]]), **LOWER_FLAGS), 0
+                r1 = np.ascontiguousarray(lwj.record(pj))
+                rj, jj = ctx.solve(np.array([0, len(r1)], np.int64), r1, cap), 0
+            if rj["flags"][jj] & _lib.F_TRACE_TRUNCATED:
+                # the reference's tracer sees every unsatisfiable step
+                # (search.go:173); this one would miss the steps past the
+                # largest reservation
+                warnings.warn("deppy_amd: search trace of problem %d truncated at %d words; "
+                              "the tracer sees only its first steps" % (p, TRACE_CAP_MAX),
+                              RuntimeWarning, stacklevel=3)
+            retraced[p] = (rj, jj, lwj, pj)
+    return retraced
 
 
 def _outcomes(inputs, lw, res, out, owners_in_res, tracer=None, retraced=None) -> list:
@@ -744,8 +772,11 @@ def _outcomes(inputs, lw, res, out, owners_in_res, tracer=None, retraced=None) -
             out[p] = (None, LookupErrors(lw.msg[p]))
             continue
         if traced:
-            rj, jj = retraced[p]
-            _replay_trace(tracer, variables, lw, p, rj, jj)
+            rj, jj, lwj, pj = retraced[p]
+            if lwj is None:
+                _replay_fused(tracer, variables, rj, jj)
+            else:
+                _replay_trace(tracer, variables, lwj, pj, rj, jj)
         st = int(res["status"][p])
         if st == SAT:
             inst = _lib.installed_list(res, p, len(variables))
@@ -772,21 +803,23 @@ def _outcomes(inputs, lw, res, out, owners_in_res, tracer=None, retraced=None) -
 
 
 def SolveQueries(catalog: Sequence[Variable], queries: Sequence[Sequence[Variable]],
-                 context: Optional[_lib.Context] = None) -> list:
+                 context: Optional[_lib.Context] = None, tracer: Optional[Tracer] = None) -> list:
     """Solve catalog + q for every q of queries, the catalog crossing to the
     GPU once (dp_lower_solve_shared): exactly what
-    SolveBatch([list(catalog) + list(q) for q in queries], fused=True)
-    returns, variables of the outcome being the catalog's and the query's own
-    objects."""
+    SolveBatch([list(catalog) + list(q) for q in queries], tracer=tracer,
+    fused=True) returns and shows the tracer, variables of the outcome and of
+    the tracer's positions being the catalog's and the query's own objects."""
     catalog = list(catalog)
     inputs = [catalog + list(q) for q in queries]
+    traced = tracer is not None and not isinstance(tracer, DefaultTracer)
     out: list = [None] * len(inputs)
     if not inputs:
         return out
     try:
         k32, q32, qc = encode_shared([catalog], [(0, v[len(catalog):]) for v in inputs])
     except ValueError:  # does not fit the compact wire: the expanded problems' path
-        return SolveBatch(inputs, context=context, fused=True)
+        return SolveBatch(inputs, tracer=tracer, context=context, fused=True)
+    cap = TRACE_CAP if traced else 0
     _lowering.busy = getattr(_lowering, "busy", 0) + 1
     try:
         with (contextlib.nullcontext() if context else _ctx_lock):
@@ -794,11 +827,13 @@ def SolveQueries(catalog: Sequence[Variable], queries: Sequence[Sequence[Variabl
             if _lowering.busy > 1:  # inside this thread's SolveBatch: storage of its own
                 dl = _lib.DeviceLowerer(ctx)
                 res = {k: (v.copy() if isinstance(v, np.ndarray) else v)
-                       for k, v in dl.lower_solve_shared(k32, q32, qc).items()}
+                       for k, v in dl.lower_solve_shared(k32, q32, qc, cap).items()}
                 dl.close()
             else:
-                res = _device_lowerer(ctx).lower_solve_shared(k32, q32, qc)
-        return _outcomes(inputs, _FusedLowering(res), res, out, True)
+                res = _device_lowerer(ctx).lower_solve_shared(k32, q32, qc, cap)
+        lw = _FusedLowering(res)
+        retraced = _retrace(inputs, lw, res, context, True) if traced else {}
+        return _outcomes(inputs, lw, res, out, True, tracer if traced else None, retraced)
     finally:
         _lowering.busy -= 1
 

@@ -482,6 +482,35 @@ int32_t dp_dlower_error(const dp_dlower* d, int32_t p, const char** msg);
  * as dp_lower_solve; NULL arguments return -1 without touching a device. */
 int dp_lower_solve_shared(dp_dlower* d, const dp_wire32* catalogs, const dp_wire32* queries,
                           const int32_t* query_catalog /* [queries->n_problems], -1..B-1 */, dp_solved* out);
+/* The two calls above with the search trace (WithTracer, solve.go:141-146;
+ * Tracer.Trace at every unsatisfiable search step, search.go:173): the event
+ * records dp_upload_traced documents, trace_cap words reserved per problem.
+ * The solve writes each window's traces into device memory; after the
+ * window's job a kernel packs the words that were written -- not P *
+ * trace_cap -- into page-locked memory, with the AppliedConstraint of every
+ * identity word (lit_mapping.go:69-72) looked up on the device beside it.
+ * With L = dp_lower_into(NARROW | PACKED | PINNED) of the same problems (the
+ * shared call's: dp_expand_shared's) and T = dp_solve_traced(L's batch,
+ * trace_cap), for every problem p: trace_off[p+1] - trace_off[p] ==
+ * T.trace_len[p]; those words equal T.trace[p * trace_cap ..]; at every
+ * identity word id of an event trace_var / trace_con are L.ident_var /
+ * ident_con[L.ident_off[p] + id] (-1 for an id outside [0, nid)), and -1 at
+ * every other word; every dp_solved array is what the untraced call returns,
+ * except that flags carry DP_F_TRACE_TRUNCATED exactly where T's do.  A
+ * problem with a lowering error has an empty trace.  A traced call's window
+ * is at most 256 MiB / (4 trace_cap) problems (DEPPY_FUSED_TRACE_BYTES, read
+ * per call, replaces the 256 MiB); problems left to the host are solved with
+ * dp_solve_traced in pieces under the same bound.  trace_cap outside 1 ..
+ * 1<<24 returns -1 with a text; everything else as the untraced calls. */
+typedef struct dp_traced {      /* owned by the dp_dlower, page-locked, valid until its next call */
+  const int64_t* trace_off;     /* [P+1]; problem p's event records are trace[trace_off[p] .. trace_off[p+1]) */
+  const int32_t* trace;         /* dense; the records dp_upload_traced documents: [n, vars.., m, identities..] */
+  const int32_t* trace_var;     /* parallel to trace: at an identity word its owner's variable index, elsewhere -1 */
+  const int32_t* trace_con;     /* ... and the index in that variable's Constraints(), elsewhere -1 */
+} dp_traced;
+int dp_lower_solve_traced(dp_dlower* d, const dp_wire32* wire, int32_t trace_cap, dp_solved* out, dp_traced* traced);
+int dp_lower_solve_shared_traced(dp_dlower* d, const dp_wire32* catalogs, const dp_wire32* queries,
+                                 const int32_t* query_catalog, int32_t trace_cap, dp_solved* out, dp_traced* traced);
 /* The expanded problems of such a call as a 64-bit wire batch, made on the
  * host without a device: what dp_lower_solve_shared is defined against, and what its host
  * fallback lowers.  The handle owns the wire's arrays; the string table is
@@ -741,6 +770,15 @@ int dp_plan_order(const dp_batch* b, int32_t opt_flags, int32_t* order, int32_t*
  *     device memory. */
 int dp_plan_order_heads(const int32_t* heads, const int64_t* rec_off, int32_t n, int32_t opt_flags,
                         int32_t* order, int32_t* launch_first);
+/*   dp_trace_owners_host: the walk of the trace pack kernel
+ *     (dp_lower_solve_traced), on the host: for a trace of len words, the
+ *     owner ivs / ics[id] of every event's identity words into out_var /
+ *     out_con[len] (-1 for an id outside [0, nid)), and -1 at every other
+ *     word.  A negative count or an event running past len ends the walk: the
+ *     words from there on get -1.  Returns 0, or -1 for a negative len or
+ *     nid or a missing array. */
+int dp_trace_owners_host(const int32_t* trace, int32_t len, int32_t nid, const int32_t* ivs, const int32_t* ics,
+                         int32_t* out_var, int32_t* out_con);
 
 /* Device time of the solve kernel(s) of the last waited launch (dp_run,
  * dp_wait, dp_solve), measured with HIP events on its stream (max over devices). */
