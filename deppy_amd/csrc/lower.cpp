@@ -253,6 +253,7 @@ struct Fast {
   uint8_t* src;
   bool src_ok;
   int32_t nc, ncl, nk, nkl, nch, nchl, na, nid;
+  bool pos_row;  // a both-positive Or's row: the record carries DP_H_NVU
   void reset(size_t nv, size_t C, size_t A) {
     const size_t need = (C + 1) + (A + C) + C + (C + 1) + A + C + C + (nv + 1) + (C + 1) + A + nv + 5 * C + 2 * (A + 1) +
                         (C + 4) / 4;
@@ -270,6 +271,7 @@ struct Fast {
     first_c = store64.data();
     nc = ncl = nk = nkl = nch = nchl = na = nid = 0;
     src_ok = true;
+    pos_row = false;
     clause_off[0] = card_off[0] = var_choice_off[0] = choice_off[0] = 0;
   }
   void close_clause(int32_t id) {
@@ -327,6 +329,10 @@ struct alignas(128) Work {  // per-thread scratch
   // AtMost networks (Lowerer::network_rows): next auxiliary variable, a
   // gate's cone and the walk's marks
   int32_t naux = 0;
+  // Or rows of the record under construction (lower_one): a mixed-polarity
+  // one (a Dependency's shape without a choice list: explicit lists), an
+  // all-positive one (DP_H_NVU)
+  bool mixed_or_row = false, pos_row = false;
   std::vector<int32_t> cone, walk;
   std::vector<uint8_t> vis;
   std::vector<std::string> errs;
@@ -351,17 +357,23 @@ struct alignas(128) Work {  // per-thread scratch
 //                                  an input, so equal terms <=> equal sequences)
 //   K_CARD n, set  !sorted[n]      AtMost(n; m distinct vars), m >= 3 (hashed)
 //   K_F            F               AtMost(n < 0; ...)
+//   K_OR {a,b}     !And(!x_a,!x_b) Or(a, b), both positive            (a != b)
+// An Or on one variable is K_POS, K_NEG or the constant T, and one of two
+// negated literals is K_CONF.  An Or of one negated and one positive literal,
+// Or(!x_a, x_b), is the term of Dependency(a; b) of any subject's Or, which
+// this path matches only against lists of the same subject: a problem holding
+// one goes to the exact path.
 // Terms of different keys compute different Boolean functions, so they are
 // different terms: !sorted[n] of Batcher's network over m distinct inputs is
 // "at most n of the m", antimonotone and dependent on all m (0 <= n < m); a
 // Dependency chain with s not among d is increasing in every d it names (or
-// the constant T once s recurs); Mandatory is increasing, the others are
-// antimonotone in fewer variables.  What the keys cannot decide goes to the
+// the constant T once s recurs); Mandatory is increasing in one variable and
+// K_OR in two, the others are antimonotone in fewer variables.  What the keys cannot decide goes to the
 // exact path (lower_one, the full AIG): an AtMost with a repeated variable,
 // two AtMosts over one set and bound in different orders (same function,
 // structure unknown), a hashed key that matches a different sequence, and any
 // lookup error.
-enum : uint64_t { K_F = 0, K_POS = 1, K_NEG = 2, K_CONF = 3, K_NOR = 4, K_DEP = 5, K_CARD = 6 };
+enum : uint64_t { K_F = 0, K_POS = 1, K_NEG = 2, K_CONF = 3, K_NOR = 4, K_DEP = 5, K_CARD = 6, K_OR = 7 };
 inline uint64_t key1(uint64_t tag, uint32_t a) { return tag << 60 | a; }
 inline uint64_t key2(uint64_t tag, uint32_t a, uint32_t b) {
   if (a > b) std::swap(a, b);
@@ -653,7 +665,9 @@ struct Lowerer {
   // start_chunk copies such batches to the device without staging them).
   // src: the DP_FMT_P16D sources of its choice lists when the caller knows
   // them (lower_fast), else nullptr (pack16 derives them: choice_sources).
-  void narrow_last(Out& O, size_t base, const uint8_t* src = nullptr) const {
+  // explicit_lists: the record holds a mixed-polarity Or's row, which has a
+  // Dependency row's shape and no choice list, so no implied-list form.
+  void narrow_last(Out& O, size_t base, const uint8_t* src = nullptr, bool explicit_lists = false) const {
     if (!narrow || O.nrec == base) return;
     int32_t* r = O.rec.data() + base;
     const int64_t words = r[DP_H_WORDS];
@@ -669,7 +683,7 @@ struct Lowerer {
         r[DP_H_FMT] = DP_FMT_I32W;
         phys = words + ext;
       }
-    } else if (packed && pack16(r, src)) {
+    } else if (packed && pack16(r, src, explicit_lists)) {
       const int64_t p8w = p8 ? pack8(r) : 0;
       phys = p8w ? p8w : dp_rec_phys_words(r);
     } else if (dp_rec_fits16(r)) {
@@ -691,16 +705,18 @@ struct Lowerer {
   // The int32 record r (fits16) in a packed form, in place, if it allows it
   // (every identity one row, each row kind's identities ascending, lengths
   // below 256, DP_P16_TAIL_MAX): DP_FMT_P16D when its dependency rows imply
-  // its choice lists, else DP_FMT_P16.  False leaves r as it is.
-  static bool pack16(int32_t* r, const uint8_t* src_known = nullptr) {
+  // its choice lists (never when explicit_lists), else DP_FMT_P16.  False
+  // leaves r as it is.
+  static bool pack16(int32_t* r, const uint8_t* src_known = nullptr, bool explicit_lists = false) {
     if (!dp_rec_fits16(r) || r[DP_H_NID] != r[DP_H_NC] + r[DP_H_NK]) return false;
     const dp_rec_layout L = dp_rec_layout_of(r);
     const int32_t nc = r[DP_H_NC], nk = r[DP_H_NK], nv = r[DP_H_NV], nch = r[DP_H_NCH], nid = r[DP_H_NID];
     // DP_FMT_P16D when the dependency rows imply the choice lists exactly
     static thread_local std::vector<uint8_t> srcs;
     const uint8_t* sp = src_known;
-    bool derived = !no_p16d() && sp;
-    if (!no_p16d() && !sp) {
+    const bool implied = !no_p16d() && !explicit_lists;
+    bool derived = implied && sp;
+    if (implied && !sp) {
       if (srcs.size() < (size_t)nch + 1) srcs.resize((size_t)nch + 1);
       derived = choice_sources(r, L, srcs.data());
       sp = srcs.data();
@@ -790,6 +806,7 @@ struct Lowerer {
     hdr[DP_H_NCL] = F.ncl;
     hdr[DP_H_NKL] = F.nkl;
     hdr[DP_H_NCHL] = F.nchl;
+    hdr[DP_H_NVU] = F.pos_row ? nv : 0;
     hdr[DP_H_WORDS] = dp_rec_layout_of(hdr).words;
     if (!lds_image(hdr, ldsg)) return false;  // (fits16 included)
     for (int32_t i = 0; i < F.nc; ++i)
@@ -902,6 +919,7 @@ struct Lowerer {
     W.card_off.assign(1, 0); W.card_lits.clear(); W.card_bound.clear(); W.card_id.clear();
     W.errs.clear();
     W.naux = nv;
+    W.mixed_or_row = W.pos_row = false;
 
     // pass 2: Apply every constraint (lit_mapping.go:59-74)
     for (int vi = 0; vi < nv; ++vi) {
@@ -937,6 +955,12 @@ struct Lowerer {
               W.ms.push_back(Aig::input(d));
             }
             if (!bad) m = leq(aig, W, w.con_n[c]);
+            break;
+          }
+          case DP_OR: {  // Or(ls, lo), each side negated by its flag (include/deppy_hip.h)
+            int32_t t = lit_of(w.con_arg[a0]);
+            if (t < 0) bad = true;
+            else m = aig.Or(Aig::input(vi) ^ (w.con_n[c] & 1), Aig::input(t) ^ ((w.con_n[c] >> 1) & 1));
             break;
           }
         }
@@ -981,8 +1005,8 @@ struct Lowerer {
     }
     W.var_choice_off.resize((size_t)W.naux + 1, W.var_choice_off.back());  // auxiliaries: no choices
     const size_t base = O.nrec;
-    emit_record(W, O, W.naux, W.naux > nv ? nv : 0);
-    narrow_last(O, base);
+    emit_record(W, O, W.naux, W.naux > nv || W.pos_row ? nv : 0);
+    narrow_last(O, base, nullptr, W.mixed_or_row);
   }
 
   // lower_one's exact result without the And-inverter graph, from the
@@ -1029,7 +1053,7 @@ struct Lowerer {
     // arrays could alias F's int32 counters, which would then be reloaded
     // and stored around every element
     int32_t nc = 0, ncl = 0, nk = 0, nkl = 0, nch = 0, nchl = 0, na = 0, nid = 0;
-    bool src_ok = true;
+    bool src_ok = true, pos_row = false;
     int32_t* const clause_off = F.clause_off;
     int32_t* const clause_lits = F.clause_lits;
     int32_t* const clause_id = F.clause_id;
@@ -1178,6 +1202,21 @@ struct Lowerer {
             }
             break;
           }
+          case DP_OR: {
+            const int32_t fl = con_n[c];
+            if (a1 - a0 != 1 || fl < 0 || fl > 3) return -1;
+            const int32_t t = var(con_arg[a0]);
+            if (t < 0) return t == -2 ? -1 : 0;
+            if (fl == 1 || fl == 2) {  // mixed signs: T on one variable, else the exact path
+              if (t != vi) return 0;
+              taut = true;
+              break;
+            }
+            seq[ns++] = t;
+            key = t == vi ? key1(fl ? K_NEG : K_POS, (uint32_t)vi)
+                          : key2(fl ? K_CONF : K_OR, (uint32_t)vi, (uint32_t)t);
+            break;
+          }
           default:
             return -1;
         }
@@ -1202,10 +1241,12 @@ struct Lowerer {
         } else if (tg == K_POS || tg == K_NEG) {
           clause_lits[ncl++] = 2 * (int32_t)(key & 0x3fffffff) + (tg == K_NEG);
           close_clause(id);
-        } else if (kind == DP_CONFLICT) {
-          clause_lits[ncl++] = 2 * vi + 1;
-          clause_lits[ncl++] = 2 * seq[0] + 1;
+        } else if (kind == DP_CONFLICT || kind == DP_OR) {  // (~s ~t), or K_OR's (s t)
+          const int32_t neg = tg == K_CONF;
+          clause_lits[ncl++] = 2 * vi + neg;
+          clause_lits[ncl++] = 2 * seq[0] + neg;
           close_clause(id);
+          pos_row |= !neg;
         } else {  // AtMost over distinct variables
           std::copy(seq, seq + ns, card_lits + nkl);
           nkl += ns;
@@ -1219,6 +1260,7 @@ struct Lowerer {
     }
     F.nc = nc; F.ncl = ncl; F.nk = nk; F.nkl = nkl; F.nch = nch; F.nchl = nchl; F.na = na; F.nid = nid;
     F.src_ok = src_ok;
+    F.pos_row = pos_row;
     if (emit_p16d(F, O, nv)) return 1;
     const size_t base = O.nrec;
     emit_fast(F, O, nv);
@@ -1239,6 +1281,7 @@ struct Lowerer {
     hdr[DP_H_NCL] = F.ncl;
     hdr[DP_H_NKL] = F.nkl;
     hdr[DP_H_NCHL] = F.nchl;
+    hdr[DP_H_NVU] = F.pos_row ? nv : 0;
     const dp_rec_layout L = dp_rec_layout_of(hdr);
     hdr[DP_H_WORDS] = L.words;
     int32_t* r = O.extend((size_t)L.words);
@@ -1353,6 +1396,13 @@ struct Lowerer {
       W.card_off.push_back((int32_t)W.card_lits.size());
       W.card_bound.push_back(n);
       W.card_id.push_back(ident);
+    } else if (kind == DP_OR) {  // (ls lo), n its flags; of mixed signs the negative literal first
+      const int32_t ls = 2 * s + (n & 1), lo = 2 * var_of(a0) + ((n >> 1) & 1);
+      W.clause_lits.push_back(n == 2 ? lo : ls);
+      W.clause_lits.push_back(n == 2 ? ls : lo);
+      close_clause();
+      W.mixed_or_row |= n == 1 || n == 2;
+      W.pos_row |= n == 0;
     }
   }
 
@@ -1555,10 +1605,11 @@ static bool problem_ok(const dp_wire* w, int32_t p) {
   if (v1 == v0) return true;
   for (int64_t c = w->var_con_off[v0]; c < w->var_con_off[v1]; ++c) {
     int32_t k = w->con_kind[c];
-    if (k < DP_MANDATORY || k > DP_ATMOST) return false;
+    if (k < DP_MANDATORY || k > DP_OR) return false;
     int64_t na = w->con_arg_off[c + 1] - w->con_arg_off[c];
     if (na < 0) return false;
-    if (k == DP_CONFLICT && na != 1) return false;
+    if ((k == DP_CONFLICT || k == DP_OR) && na != 1) return false;
+    if (k == DP_OR && (w->con_n[c] < 0 || w->con_n[c] > 3)) return false;  // its flags
     if ((k == DP_MANDATORY || k == DP_PROHIBITED) && na != 0) return false;
     for (int64_t a = w->con_arg_off[c]; a < w->con_arg_off[c + 1]; ++a)
       if (w->con_arg[a] < 0 || w->con_arg[a] >= w->n_strs) return false;

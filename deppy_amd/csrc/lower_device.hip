@@ -90,12 +90,18 @@ constexpr int DL_KH = 1024;  // identity-key slots (>= 2 DL_C)
 constexpr int DL_SLOT = (DL_KH * 16) / 4;
 constexpr int DL_T = 64;  // one wavefront per problem
 
-// canonical keys, as lower.cpp's
-enum : uint64_t { K_F = 0, K_POS = 1, K_NEG = 2, K_CONF = 3, K_NOR = 4, K_DEP = 5, K_CARD = 6 };
+// canonical keys, as lower.cpp's, and one more: K_IMP (a, b), the ordered
+// pair of !And(x_a, !x_b), the term of Dependency(a; b) (one candidate, not
+// its subject; exact, where longer lists are hashed under K_DEP) and of the
+// mixed-polarity Or(!x_a, x_b) of either subject, which so meet in the table
+enum : uint64_t { K_F = 0, K_POS = 1, K_NEG = 2, K_CONF = 3, K_NOR = 4, K_DEP = 5, K_CARD = 6, K_OR = 7, K_IMP = 8 };
 __device__ __forceinline__ uint64_t key1(uint64_t tag, uint32_t a) { return tag << 60 | a; }
 __device__ __forceinline__ uint64_t key2(uint64_t tag, uint32_t a, uint32_t b) {
   const uint32_t lo = a < b ? a : b, hi = a < b ? b : a;
   return tag << 60 | (uint64_t)lo << 30 | hi;
+}
+__device__ __forceinline__ uint64_t key2o(uint64_t tag, uint32_t a, uint32_t b) {
+  return tag << 60 | (uint64_t)a << 30 | b;
 }
 __device__ __forceinline__ uint64_t hmix(uint64_t h, uint64_t x) {
   h ^= x + 0x9e3779b97f4a7c15ULL;
@@ -104,16 +110,19 @@ __device__ __forceinline__ uint64_t hmix(uint64_t h, uint64_t x) {
 }
 __device__ __forceinline__ uint64_t keyh(uint64_t tag, uint64_t h) { return tag << 60 | (h & ((1ULL << 60) - 1)); }
 
-// a constraint's row if it is its key's first writer (cmeta)
+// a constraint's row if it is its key's first writer (cmeta); flags: an Or's
+// (include/deppy_hip.h DP_OR), which give its row's signs
 enum { RT_SKIP = 0, RT_CLAUSE = 1, RT_CARD = 2 };
-__device__ __forceinline__ uint32_t meta(int rt, bool hashed, bool list, int kind, int len) {
-  return (uint32_t)rt | (hashed ? 4u : 0u) | (list ? 8u : 0u) | (uint32_t)kind << 4 | (uint32_t)len << 8;
+__device__ __forceinline__ uint32_t meta(int rt, bool hashed, bool list, int kind, int len, int flags = 0) {
+  return (uint32_t)rt | (hashed ? 4u : 0u) | (list ? 8u : 0u) | (uint32_t)kind << 4 | (uint32_t)len << 8 |
+         (uint32_t)flags << 30;
 }
 __device__ __forceinline__ int m_rt(uint32_t m) { return (int)(m & 3u); }
 __device__ __forceinline__ bool m_hashed(uint32_t m) { return (m & 4u) != 0; }
 __device__ __forceinline__ bool m_list(uint32_t m) { return (m & 8u) != 0; }
 __device__ __forceinline__ int m_kind(uint32_t m) { return (int)((m >> 4) & 15u); }
-__device__ __forceinline__ int m_len(uint32_t m) { return (int)(m >> 8); }
+__device__ __forceinline__ int m_len(uint32_t m) { return (int)((m >> 8) & 0x3fffffu); }
+__device__ __forceinline__ int m_flags(uint32_t m) { return (int)(m >> 30); }
 
 // Arrays live in phases: the identifier table (1) shares its words with the
 // rows (3-4), the key table (2-3) with the record (4), which keeps the
@@ -461,6 +470,9 @@ __global__ void __launch_bounds__(DL_T) lower_kernel(DlArgs a) {
           // rows, so the record is DP_FMT_P16 with the lists explicit
           m = meta(RT_SKIP, false, true, kind, 0);
           S.p16 = 1;
+        } else if (ns == 1) {  // (~s d): K_IMP, where a mixed-polarity Or meets it
+          key = key2o(K_IMP, (uint32_t)vi, (uint32_t)S.ca[a0]);
+          m = meta(RT_CLAUSE, false, true, kind, 2);
         } else {
           // the row (~s, d1..dn), each candidate once; s among the later
           // candidates folds the row to T while the identity stays (not a
@@ -543,6 +555,26 @@ __global__ void __launch_bounds__(DL_T) lower_kernel(DlArgs a) {
             }
             break;
           }
+          case DP_OR: {  // n: its flags (1 subject negated, 2 operand negated)
+            bad = ns != 1 || n < 0 || n > 3;
+            if (bad) break;
+            const int t = S.ca[a0];
+            const bool mixed = n == 1 || n == 2;
+            if (t == vi) {
+              if (mixed) {  // Or(x, ~x) = T: no identity
+                m = meta(RT_SKIP, false, false, kind, 0);
+              } else {
+                key = key1(n ? K_NEG : K_POS, (uint32_t)vi);
+                m = meta(RT_CLAUSE, false, false, kind, 1);
+              }
+            } else {
+              // (of mixed signs: the negated variable first)
+              if (mixed) key = key2o(K_IMP, (uint32_t)(n == 1 ? vi : t), (uint32_t)(n == 1 ? t : vi));
+              else key = key2(n ? K_CONF : K_OR, (uint32_t)vi, (uint32_t)t);
+              m = meta(RT_CLAUSE, false, false, kind, 2, n);
+            }
+            break;
+          }
           default:
             bad = true;
         }
@@ -590,6 +622,7 @@ __global__ void __launch_bounds__(DL_T) lower_kernel(DlArgs a) {
   // ---- 3. numbering in constraint order ----
   int nid = 0, nc = 0, ncl = 0, nk = 0, nkl = 0, nch = 0, nchl = 0;
   bool b1 = true, nib = true;
+  bool posrow = false;  // a row of two positive literals (a both-positive Or's): DP_H_NVU
   for (int c0 = 0; c0 < C; c0 += DL_T) {
     const int c = c0 + lane;
     const bool act = c < C;
@@ -641,11 +674,18 @@ __global__ void __launch_bounds__(DL_T) lower_kernel(DlArgs a) {
     __syncthreads();  // the chunk's cid / clist before their readers
     bool far = false;
     if (isl) {
-      const int d = isf || s < 0 ? 0 : k - S.clist[first];
+      // (a key first written by an Or has a row and no list to repeat: the
+      // lists are explicit then, below)
+      const int d = isf || s < 0 || !m_list(S.cmeta[first]) ? 0 : k - S.clist[first];
       far = d > 255;
       S.src[k] = (uint8_t)d;
     }
-    if (__ballot(far) && lane == 0) S.p16 = 1;  // a repeat too far back for a source byte
+    // a repeat too far back for a source byte; a first-writer Or of mixed
+    // signs, whose row has a Dependency row's shape and no list
+    const int fl = m_flags(m);
+    const bool or2 = isc && kind == DP_OR && rlen == 2;
+    if (__ballot(far || (or2 && (fl == 1 || fl == 2))) && lane == 0) S.p16 = 1;
+    posrow = posrow || __ballot(or2 && fl == 0) != 0;
     if (isc) {
       S.clen[crow] = (uint8_t)rlen;
       if (kind == DP_DEPENDENCY && ns > 0) {
@@ -659,9 +699,11 @@ __global__ void __launch_bounds__(DL_T) lower_kernel(DlArgs a) {
       } else if (rlen == 1) {
         const uint64_t key = S.kkey[s] - 1ull;
         S.clit[cat] = (int16_t)(2 * (int)(key & 0x3fffffffULL) + ((key >> 60) == K_NEG ? 1 : 0));
-      } else if (rlen == 2) {  // Conflict(a, b): (~a ~b)
-        S.clit[cat] = (int16_t)(2 * vi + 1);
-        S.clit[cat + 1] = (int16_t)(2 * S.ca[a0] + 1);
+      } else if (rlen == 2) {  // Conflict(a, b): (~a ~b); an Or: its flags' signs, a lone negative literal first
+        const int sg = kind == DP_OR ? fl : 3;
+        const int ls = 2 * vi + (sg & 1), lo = 2 * S.ca[a0] + (sg >> 1);
+        S.clit[cat] = (int16_t)(sg == 2 ? lo : ls);
+        S.clit[cat + 1] = (int16_t)(sg == 2 ? ls : lo);
       }
     }
     bool kb1 = true;
@@ -709,6 +751,7 @@ __global__ void __launch_bounds__(DL_T) lower_kernel(DlArgs a) {
   h[DP_H_NCL] = ncl;
   h[DP_H_NKL] = nkl;
   h[DP_H_NCHL] = nchl;
+  h[DP_H_NVU] = posrow ? nv : 0;
   h[DP_H_WORDS] = DP_H_SIZE + (nc + 1) + ncl + nc + (nk + 1) + nkl + 2 * nk + (nv + 1) + (nch + 1) + nchl + na;
   // one wavefront per problem (placement.hpp lds_image)
   // (the whole working set, LDS and scratch, as placement.hpp one_wave compares it)

@@ -31,7 +31,7 @@ import numpy as np
 
 from . import _lib
 
-MANDATORY, PROHIBITED, DEPENDENCY, CONFLICT, ATMOST = 1, 2, 3, 4, 5
+MANDATORY, PROHIBITED, DEPENDENCY, CONFLICT, ATMOST, OR = 1, 2, 3, 4, 5, 6
 SAT, UNSAT, INCOMPLETE, ERROR = 1, -1, 0, -2
 
 
@@ -96,6 +96,8 @@ class Constraint:
             return "%s conflicts with %s" % (s, self.ids[0])  # :145
         if self.kind == ATMOST:
             return "%s permits at most %d of %s" % (s, self.n, ", ".join(self.ids))  # :173-177
+        if self.kind == OR:  # (this project's text: the reference has no Or)
+            return "%s%s or %s%s" % ("not " if self.n & 1 else "", s, "not " if self.n & 2 else "", self.ids[0])
         return ""
 
     def Order(self) -> Optional[list]:
@@ -109,7 +111,10 @@ class Constraint:
 
     def __repr__(self):
         names = {MANDATORY: "Mandatory", PROHIBITED: "Prohibited", DEPENDENCY: "Dependency",
-                 CONFLICT: "Conflict", ATMOST: "AtMost"}
+                 CONFLICT: "Conflict", ATMOST: "AtMost", OR: "Or"}
+        if self.kind == OR:
+            return "Or(%r, isSubjectNegated=%r, isOperandNegated=%r)" % (
+                str(self.ids[0]), bool(self.n & 1), bool(self.n & 2))
         args = ([str(self.n)] if self.kind == ATMOST else []) + [repr(str(i)) for i in self.ids]
         return "%s(%s)" % (names.get(self.kind, "?"), ", ".join(args))
 
@@ -132,6 +137,13 @@ def Conflict(id) -> Constraint:
 
 def AtMost(n: int, *ids) -> Constraint:
     return Constraint(ATMOST, _ids(ids), int(n))
+
+
+def Or(operand, isSubjectNegated: bool = False, isOperandNegated: bool = False) -> Constraint:
+    """An extension (later deppy releases; include/deppy_hip.h DP_OR): holds
+    when the subject or the operand does, either side negated by its flag.  No
+    anchor and no Order(); n carries the flags (1: subject, 2: operand)."""
+    return Constraint(OR, (Identifier(operand),), (1 if isSubjectNegated else 0) | (2 if isOperandNegated else 0))
 
 
 class zeroConstraint(Constraint):

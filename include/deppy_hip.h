@@ -47,13 +47,30 @@ extern "C" {
 /* ------------------------------------------------------------------------ */
 
 /* Constraint kinds: pkg/sat/constraints.go:74 (Mandatory), :100 (Prohibited),
- * :138 (Dependency), :163 (Conflict), :199 (AtMost). */
+ * :138 (Dependency), :163 (Conflict), :199 (AtMost).
+ *
+ * DP_OR is an extension (later deppy releases have an Or; the reference this
+ * project follows has none, so its semantics are defined here): on subject s
+ * it holds when ls or lo holds, ls = x_s (negated with flag bit 0), lo =
+ * x_operand (negated with flag bit 1).  It has exactly one argument, the
+ * operand, and carries its flags in con_n: 0..3, any other value is a
+ * malformed wire.  In dp_wire32 that is con_kn = 6 | flags << 3.  It is no
+ * anchor and makes no choice list.  Its assumed literal is
+ * Or(ls, lo) = !And(!ls, !lo), so Or(!s, !o) shares Conflict(s, o)'s
+ * identity, Or(!a, b) shares Dependency(a; b)'s, and Or(s, s) / Or(!s, !s)
+ * share Mandatory's / Prohibited's; Or(s, !s) is the constant T (no
+ * identity, no row).  An Or of two positive literals over different
+ * variables lowers to a clause row without a negative literal: records
+ * holding one carry DP_H_NVU = the input's variable count, which makes the
+ * solve kernels scan every row for a violated one. */
 enum dp_kind {
   DP_MANDATORY = 1,
   DP_PROHIBITED = 2,
   DP_DEPENDENCY = 3, /* args = candidate identifiers in preference order */
   DP_CONFLICT = 4,   /* args = exactly one identifier                    */
-  DP_ATMOST = 5      /* args = identifiers; n = bound                     */
+  DP_ATMOST = 5,     /* args = identifiers; n = bound                     */
+  DP_OR = 6          /* args = exactly one identifier (the operand);
+                        n = flags: 1 subject negated, 2 operand negated   */
 };
 
 /* A batch of independent problems.  Every problem is the []Variable handed to
@@ -69,7 +86,8 @@ typedef struct dp_wire {
   const int64_t* var_id;       /* [n_vars]   string index of Identifier  */
   const int64_t* var_con_off;  /* [n_vars+1] -> constraints             */
   const int32_t* con_kind;     /* [n_cons]   enum dp_kind               */
-  const int32_t* con_n;        /* [n_cons]   AtMost bound (else ignored) */
+  const int32_t* con_n;        /* [n_cons]   AtMost bound; DP_OR's flags (0..3);
+                                  else ignored                            */
   const int64_t* con_arg_off;  /* [n_cons+1] -> con_arg                  */
   const int64_t* con_arg;      /* [n_args]   string index               */
   int64_t n_strs;
@@ -386,7 +404,8 @@ typedef struct dp_wire32 {
                                    (NULL when var_id16 is given)          */
   const uint16_t* var_ncon;     /* [n_vars]  constraints of the variable   */
   const int32_t* con_kn;        /* [n_cons]  enum dp_kind | bound << 3 (the
-                                   AtMost bound, arithmetic shift)        */
+                                   AtMost bound, arithmetic shift; DP_OR:
+                                   6 | flags << 3)                        */
   const uint16_t* con_nargs;    /* [n_cons]  arguments of the constraint   */
   const int32_t* con_arg;       /* [n_args]  string index (NULL when
                                    con_arg16 is given)                    */
