@@ -901,9 +901,13 @@ class Catalog:
     queries, tracer=tracer) returns, and shows the tracer the same events.
     The string indices are 32 bits wide, so the width never changes as
     queries bring new identifiers.  The context (the process-wide one by
-    default) must outlive the Catalog; close() frees the device's copy."""
+    default) must outlive the Catalog; close() frees the device's copy.
 
-    def __init__(self, variables: Sequence[Variable], context: Optional[_lib.Context] = None):
+    open=True (DP_PREPARE_OPEN) also prepares a catalog whose constraints
+    name identifiers that only the queries define -- a platform, an installed
+    set: those constraints wait for each query and are finished with it."""
+
+    def __init__(self, variables: Sequence[Variable], context: Optional[_lib.Context] = None, open: bool = False):
         self.variables = list(variables)
         self._context = context
         self._lock = threading.Lock()
@@ -918,7 +922,7 @@ class Catalog:
             return
         with (contextlib.nullcontext() if context else _ctx_lock):
             self._dl = _lib.DeviceLowerer(context or device_context())
-            self._prep = self._dl.prepare(k32)
+            self._prep = self._dl.prepare(k32, open=open)
 
     @property
     def prepared(self) -> bool:
